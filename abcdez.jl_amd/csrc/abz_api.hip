@@ -545,7 +545,20 @@ static int timing_consume(abcdez_ctx* ctx, long long n, long long done) {
     const int slot = (int)(ctx->ev_head % ABZ_GROUP_MAX);
     if (done >= 0 && !ctx->ev_group[slot] && ctx->ev_sweep[slot] >= done) continue;
     float ms = 0.f;
-    ABZ_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev[2 * slot], ctx->ev[2 * slot + 1]));
+    const hipError_t e = hipEventElapsedTime(&ms, ctx->ev[2 * slot], ctx->ev[2 * slot + 1]);
+    if (e == hipErrorNotReady) {
+      /* seen once (a bench run ended here with "device not ready"), never reproduced.  What the code establishes: the read-back that
+       * brought us here polls a word the publish kernel wrote BEHIND this pair in stream order, without synchronising the stream, so
+       * the sweeps have run.  SUPPOSED: the runtime had not yet taken note of the closing event's signal at that moment.  Either
+       * way waiting for that event (microseconds: its work is done) and reading again is right; the refused query must not stay
+       * behind as the thread's last error, which the next launch check would report */
+      (void)hipGetLastError();
+      ABZ_HIP_CHECK(hipEventSynchronize(ctx->ev[2 * slot + 1]));
+      ABZ_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev[2 * slot], ctx->ev[2 * slot + 1]));
+    } else if (e != hipSuccess) {
+      abz_set_error(std::string("hipEventElapsedTime (sweep timing): ") + hipGetErrorString(e));
+      return -2;
+    }
     /* a pair around a whole group of sweeps (mode 3) stands for the `done` launches that did work, each of ev_units updates; the
      * one-block checks between them are inside the pair, so milliseconds / launches is an UPPER bound of the sweep's duration */
     const long long nl = ctx->ev_group[slot] ? (done > 0 ? done : ctx->ev_group[slot]) : 1;

@@ -9,7 +9,14 @@ abcdesmc with alpha = 0.95, delta_ess = 0.5, Kmcmc = 3, IndicatorStrict, 2^22 pa
 population (one library call), (resample), up to Kmcmc DE-Metropolis sweeps (one library call).  One particle-update = one alive
 particle through one sweep.  State is resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config smc32|mc1d|lv|evidence1d]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config smc32|mc1d|lv|evidence1d] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed steps, the JSON line (with the sweep
+kernel's `roofline` figures from the HIP events of the timed steps themselves).  `--full` adds everything that takes a run of its
+own: the whole run from a fresh population to eps_target (`whole_run`, `errors_vs_exact`), the CPU-oracle baselines
+(`cpu_baseline`, `cpu_baseline_reference_faithful`), the arithmetic-free access pattern (`roofline.pattern_ceiling`) and the
+other single-GPU configurations (`other_configs`); the `--no-*` options switch single parts of it off again.
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
 
 The other single-GPU configurations of BASELINE.json print the same JSON shape:
     mc1d        configs[1]: 1-D Normal, abcdemc, 2^20 particles (step = one generation, mc:134-161)
@@ -61,6 +68,13 @@ def profile_json(name):
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the whole run to eps_target with its log-Z / posterior-mean "
+                        "errors, the CPU-oracle baselines, the access-pattern ceiling of the roofline and (default configuration) the "
+                        "other single-GPU configurations; each has a --no-* option of its own")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last of them computed as DIR/<name>.npy (float64): the generation's "
+                        "scalars and the population a caller would download, a fixed seeded sample of its particles when it is large")
     p.add_argument("--no-pattern", action="store_true",
                    help="do not run tools/layout_bench for roofline.pattern_ceiling (profiling runs: keeps its kernels out of the trace)")
     p.add_argument("--steps", type=int, default=None)
@@ -90,7 +104,10 @@ def parse():
                         "generation (default); 2 = a pair of its own around ONE sweep of every 2nd generation (rounds 2-4)")
     p.add_argument("--force-collectives", action="store_true",
                    help="diagnostic: run the sharded code path (RCCL flag all-gather + replay) in a group of one rank")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:
+        args.no_pattern = args.no_cpu_baseline = args.no_whole_run = args.no_other_configs = True
+    return args
 
 
 class Generation:
@@ -111,6 +128,7 @@ class Generation:
         self.resamples = 0
         self.generations = 0
         self.range = (0.0, math.inf)
+        self.last = None
 
     def step(self):
         e = self.e
@@ -118,6 +136,7 @@ class Generation:
         # ESS < N delta_ess (smc:323-326); the Kmcmc sweeps (smc:336-353) -- one engine call, on one GPU one library call
         g = e.smc_generation(self.alpha, self.eps, self.eps_target, self.eps_k, e.N * self.delta_ess, self.gamma0, 1e-5, self.Kmcmc,
                              self.Kmcmc_min)
+        self.last = g
         self.eps, self.range = g["eps"], g["range"]
         self.logZ += math.log(g["wnorm"])                                                  # smc:315
         self.resamples += 1 if g["resampled"] else 0
@@ -142,6 +161,7 @@ class McGeneration:
         self.lo, self.hi = eng.extrema()                                                   # mc:146 (first generation)
         self.updates = self.sweeps = self.nsims = self.generations = self.ranked = 0
         self.first, self.converged = True, False
+        self.last = None
 
     AHEAD = 4      # abcdemc!'s loop has no data-dependent exit: the host may issue generations ahead of their results
 
@@ -159,7 +179,8 @@ class McGeneration:
             self.collect()
 
     def collect(self):
-        nsim, n_above, self.lo, self.hi, _ = self.e.mc_generation_collect()                # mc:156, mc:146
+        nsim, n_above, self.lo, self.hi, eps_pop = self.e.mc_generation_collect()          # mc:156, mc:146
+        self.last = dict(nsim=nsim, n_above=n_above, lo=self.lo, hi=self.hi, eps_pop=eps_pop)
         self.nsims += nsim
         self.complete = 1 - n_above / self.e.N
         self.converged = self.converged or self.hi <= self.eps_target
@@ -485,6 +506,50 @@ def pattern_ceiling_live(prefix, accepted_percent, positions):
     return best
 
 
+DUMP_ROWS = 1 << 17          # particles of a dumped population: 2^17 rows of 32 doubles = 32 MiB, under 40 MiB with the vectors
+
+
+def dump_outputs(path, eng, gen, cfg, write=True):
+    """--dump-outputs: what the timed path computed in its LAST step, as a caller of that path receives it -- the scalars the
+    generation call returned (`generation.npy`, names in `generation_fields.txt`) and the population it left on the device, in
+    the arrays of the drivers' result (smc:382-393, mc:166-171): theta, logpi, C (the distances), Wns, alive.  Populations of
+    more than DUMP_ROWS particles are written as a fixed sample of DUMP_ROWS positions (numpy Generator seeded with 0, sorted;
+    `index.npy`), gathered on the device; `population_sums.npy` holds the sums of C, logpi and every theta column over all
+    particles.  Everything float64; inputs and random numbers are functions of the arguments alone
+    (ModelSpec seed 1, counter-based generators), so two runs with the same arguments write the same files."""
+    import numpy as np
+    import torch
+
+    th, lp, dl = eng.state                      # (a sharded population fetches the other ranks' distances here: every rank calls)
+    if not write or gen.last is None:           # rank 0 writes; no step has run: nothing was computed
+        return
+    os.makedirs(path, exist_ok=True)
+    last = gen.last
+    if cfg["kind"] == "smc":
+        fields = {"eps": last["eps"], "wnorm": last["wnorm"], "ess": last["ess"], "n_alive": last["n_alive"], "Ki": last["Ki"],
+                  "resampled": last["resampled"], "naccs": sum(last["naccs"]), "nsims": sum(last["nsims"]),
+                  "range_lo": last["range"][0], "range_hi": last["range"][1], "logZ": gen.logZ}
+    else:
+        fields = {k: last[k] for k in ("nsim", "n_above", "lo", "hi", "eps_pop")}
+        fields["completion"] = gen.complete
+    fields.update(generations=gen.generations, updates=gen.updates)
+    np.save(os.path.join(path, "generation.npy"), np.array([float(v) for v in fields.values()], dtype=np.float64))
+    with open(os.path.join(path, "generation_fields.txt"), "w") as f:
+        f.write("\n".join(fields) + "\n")
+    N = th.shape[0]
+    idx = np.arange(N) if N <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(N, DUMP_ROWS, replace=False))
+    sel = torch.from_numpy(idx).to(th.device)
+    arrays = {"theta": th[:, :cfg["d"]], "logpi": lp, "C": dl, "index": None}
+    if eng.packed:                              # abcdemc has neither weights nor deaths
+        arrays.update(Wns=eng.wns, alive=eng.alive)
+    for name, t in arrays.items():
+        a = idx if t is None else t.index_select(0, sel).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    # the particles the sample leaves out still count: sums over the WHOLE population (C, logpi, then every column of theta)
+    sums = torch.cat([dl.sum().reshape(1), lp.sum().reshape(1), th[:, :cfg["d"]].sum(dim=0)])
+    np.save(os.path.join(path, "population_sums.npy"), sums.cpu().numpy().astype(np.float64))
+
+
 args_config = "smc32"
 
 
@@ -583,6 +648,8 @@ def run_config(args):
     updates = gen.updates - u0          # global particle-updates (all ranks)
     kern_ms, launches, units = eng.ops.get_timing()   # this rank's sweep kernel
     eng.ops.set_timing(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, gen, cfg, write=rank == 0)
     window = dict(sweeps=gen.sweeps - s0, updates=updates, naccs=getattr(gen, "naccs", 0) - a0,
                   sweep_launches=steps * (gen.Kmcmc if cfg["kind"] == "smc" else 1),     # dispatches of the sweep kernel a profiler sees in the window (a group enqueues Kmcmc; those behind a held test of smc:352 return at once)
                   resamples=getattr(gen, "resamples", 0) - r0,
@@ -753,6 +820,7 @@ def other_config(args, name):
     a = copy.copy(args)
     a.config, a.steps, a.warmup, a.particles_per_gpu, a.lanes, a.dim = name, None, None, None, 0, 32
     a.cpu_particles, a.no_pattern = None, True
+    a.dump_outputs = None                          # --dump-outputs is the headline configuration's last step, nobody else's
     a.cpu_steps = {"mc1d": 4, "lv": 3, "evidence1d": 3}[name]
     a.no_whole_run = args.no_whole_run             # every configuration's whole run: logZ / posterior-mean error (evidence1d: both models, the Bayes factor)
     deferred = []
