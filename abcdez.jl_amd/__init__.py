@@ -22,5 +22,6 @@ from .simulators import (  # noqa: F401
 )
 from .smc import abcdesmc, get_ess, load_checkpoint, quantile_type7, save_checkpoint, wsample_stratified  # noqa: F401
 from .mc import abcdemc  # noqa: F401
+from .summary import summary_reference, tile_tree_sum  # noqa: F401
 
 __version__ = "0.1.0"

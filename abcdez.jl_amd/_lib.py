@@ -95,6 +95,8 @@ PROTOTYPES = {
     "abcdez_smc_sweeps_sharded": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _u32, _i32, _f64,
                                   _pi64, _pi64, C.POINTER(_i32)],
     "abcdez_push_p": [_vp, _vp, _i64, _vp],
+    "abcdez_posterior_moments": [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _pf64, _pf64, _pi64],
+    "abcdez_posterior_quantiles": [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "abcdez_math_eval": [_vp, C.c_int, _vp, _vp, _vp, _i64],
     "abcdez_draws_eval": [_vp, C.c_int, _i64, _i64, _i64, _u32, _f64, _f64, _vp, _vp, _vp, _vp],
 }
@@ -104,6 +106,8 @@ HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _i64)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _i64, _i32, _i32)
 # symbols with a non-status return type
 OTHER_SYMBOLS = ("abcdez_version", "abcdez_rng_rounds", "abcdez_last_error", "abcdez_abi_layout")
+# added after MIN_VERSION (version 620): probed for, so that a 610 library still loads -- HipOps then lacks the device summaries
+OPTIONAL_SYMBOLS = ("abcdez_posterior_moments", "abcdez_posterior_quantiles")
 
 
 class AbcdezError(RuntimeError):
@@ -126,6 +130,8 @@ def load():
 
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in PROTOTYPES.items():
+        if name in OPTIONAL_SYMBOLS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -104,10 +104,10 @@ extern "C" {
 
 /* 400: Philox4x32-10 again, abz_model.mv, group abort; 401: abcdemc's better particle by rejection;
  * 500: abcdez_comm_* and abcdez_smc_sweeps_sharded (RCCL behind the ABI), timing mode 3; 600: abcdez_comm_init_host (a host-supplied
- * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext.  Hosts refuse a library older than the
+ * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles.  Hosts refuse a library older than the
  * header they were written against (abcdez.jl_amd/_lib.py, julia/ABCdeZHIP.jl check_abi): a signature that grew an argument links
  * against an old binary without a diagnostic. */
-int abcdez_version(void) { return 610; }
+int abcdez_version(void) { return 620; }
 int abcdez_rng_rounds(void) { return ABZ_PHILOX_ROUNDS; }
 
 /* sizeof / offsetof of the two structs that cross the boundary, so that a host that mirrors them by hand (the Julia
@@ -379,6 +379,7 @@ int abcdez_ctx_destroy(abcdez_ctx* ctx) {
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->lv_hand) (void)hipFree(ctx->lv_hand);
   if (ctx->sel_hist) (void)hipFree(ctx->sel_hist);
+  if (ctx->sum_ws) (void)hipFree(ctx->sum_ws);
   if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   if (ctx->d_block) (void)hipFree(ctx->d_block);      /* d_scal, d_sync, d_model, d_tables, d_data, d_mv */
   delete ctx;
@@ -1461,6 +1462,34 @@ int abcdez_push_p(abcdez_ctx* ctx, const double* theta, int64_t N, double* out) 
   ABZ_REQUIRE(ctx && theta && out, "push_p: null argument");
   ABZ_REQUIRE(N >= 0 && N <= ABZ_MAX_N, "push_p: N out of range");
   return abz_launch_push_p(ctx, theta, N, out);
+}
+
+/* Posterior summaries (csrc/abz_summary.hip).  Neither call touches a select enqueued ahead or the chain of asynchronous abcdemc
+ * generations: they only read the population. */
+int abcdez_posterior_moments(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                             const double* wns, int32_t want_second, double* mean, double* S, double* W, double* Q,
+                             int64_t* n_pos) {
+  ABZ_REQUIRE(ctx && slot0 && mean && W && Q && n_pos, "posterior_moments: null argument");
+  ABZ_REQUIRE(!bits || slot1, "posterior_moments: packed storage (bits) needs both row slots");
+  ABZ_REQUIRE(!want_second || S, "posterior_moments: want_second without an array for S");
+  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_moments: N out of range");
+  return abz_posterior_moments_impl(ctx, bits, N, slot0, slot1, wns, want_second != 0, mean, S, W, Q, n_pos);
+}
+
+int abcdez_posterior_quantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                               const double* wns, int32_t k, const double* probs, int32_t n_probs, double* q_out) {
+  ABZ_REQUIRE(ctx && slot0 && probs && q_out, "posterior_quantiles: null argument");
+  ABZ_REQUIRE(!bits || slot1, "posterior_quantiles: packed storage (bits) needs both row slots");
+  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_quantiles: N out of range");
+  ABZ_REQUIRE(k >= 0 && k < ctx->h_model.d, "posterior_quantiles: k must be in 0 <= k < length(prior)");
+  ABZ_REQUIRE(n_probs >= 1, "posterior_quantiles: n_probs must be at least 1");
+  for (int32_t q = 0; q < n_probs; ++q)
+    ABZ_REQUIRE(probs[q] >= 0.0 && probs[q] <= 1.0, "posterior_quantiles: p must be in [0, 1]");
+  /* the quantile is unweighted: it describes the posterior only where the positive weights are all equal */
+  ABZ_REQUIRE(!wns || ctx->h_model.abck < ABZ_K_EPA,
+              "posterior_quantiles: weighted quantiles are not provided (the Epanechnikov kernels give unequal weights; "
+              "mean and covariance work for every kernel)");
+  return abz_posterior_quantiles_impl(ctx, bits, N, slot0, slot1, wns, k, probs, n_probs, q_out);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

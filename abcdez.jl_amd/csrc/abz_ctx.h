@@ -102,6 +102,10 @@ struct abcdez_ctx {
   const void* sel_delta = nullptr;
   const void* sel_alive = nullptr;
   int64_t sel_N = 0;
+  /* posterior summaries (abz_summary.hip): partials, results, the gathered column -- a buffer of their own, so that a summary
+   * between two generations leaves the workspace and everything cached in it as it was */
+  void* sum_ws = nullptr;
+  size_t sum_ws_bytes = 0;
   /* running totals of the cumulative counter slots at the last read-back (ABZ_S_CSLOT0), by counter class */
   unsigned long long cnt_prev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   /* min / max slot bank the NEXT abcdemc sweep reduces into (the sweep resets the other one) */
@@ -331,6 +335,10 @@ int abz_launch_mc_chain_start(abcdez_ctx*, const double* delta, int64_t N, doubl
 struct abz_rank_plan { bool small_path, long_path; uint32_t ltiles; size_t ws_bytes; };
 abz_rank_plan abz_rank_plan_for(int64_t N, int64_t tail_hint, int64_t tail_bound);
 int abz_launch_push_p(abcdez_ctx*, const double*, int64_t, double*);
+int abz_posterior_moments_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                               int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
+int abz_posterior_quantiles_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                                 int k, const double* probs, int n_probs, double* q_out);
 void abz_fold_counters(abcdez_ctx*);
 /* Read-back of the first `nwords` device scalars WITHOUT the copy engine and without a stream synchronisation: a one-block
  * kernel writes them straight into the pinned host mirror and stores a sequence word last (system-scope release); the

@@ -457,6 +457,33 @@ class HipOps:
         _lib.check(self.lib, self.lib.abcdez_sync(self.ctx))
 
     # ---- blobs: stamps carried with the distances, simulated data rebuilt on demand (include/abcdez_hip.h) ----
+    def _summary_fn(self, name):
+        fn = getattr(self.lib, name, None)
+        if fn is None or fn.argtypes is None:       # a library older than 620 (_lib.OPTIONAL_SYMBOLS): no quiet fall-back
+            raise _lib.AbcdezError(f"{_lib.LIB_PATH} does not export {name} (abcdez_version() = {self.lib.abcdez_version()} < 620): "
+                                   "rebuild it (`make -C abcdez.jl_amd/csrc`)")
+        return fn
+
+    def posterior_moments(self, bits, slot0, slot1, wns, N, want_second=True):
+        """(mean[d], S[d, d] or None, W, Q, n_pos) of the population on the device; bits None: slot0 is a classic row array,
+        wns None: unit weights (include/abcdez_hip.h, abcdez_posterior_moments)"""
+        d = self.spec.d
+        mean = np.empty(d, dtype=np.float64)
+        S = np.empty((d, d), dtype=np.float64) if want_second else None
+        W, Q, n_pos = C.c_double(), C.c_double(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn("abcdez_posterior_moments")(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), 1 if want_second else 0, mean.ctypes.data,
+            S.ctypes.data if want_second else None, C.byref(W), C.byref(Q), C.byref(n_pos)))
+        return mean, S, W.value, Q.value, n_pos.value
+
+    def posterior_quantiles(self, bits, slot0, slot1, wns, N, k, probs):
+        """type-7 quantiles at ``probs`` of parameter k over the particles with a positive weight (abcdez_posterior_quantiles)"""
+        p = np.ascontiguousarray(probs, dtype=np.float64)
+        q = np.empty(p.size, dtype=np.float64)
+        _lib.check(self.lib, self._summary_fn("abcdez_posterior_quantiles")(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), int(k), p.ctypes.data, int(p.size), q.ctypes.data))
+        return q
+
     def set_stamps(self, cur, nxt):
         _lib.check(self.lib, self.lib.abcdez_ctx_set_stamps(self.ctx, _ptr(cur), _ptr(nxt)))
 
@@ -1239,6 +1266,35 @@ class PopulationEngine:
             return th.mean(dim=0).cpu().numpy()
         w = self.wns
         return ((w[:, None] * th).sum(dim=0) / w.sum()).cpu().numpy()
+
+    def posterior_summary(self, cov: bool = True, corrected: bool = True, quantiles=()):
+        """Posterior summaries of the population where it lives (include/abcdez_spec.h, "posterior summaries"): a record with
+        ``mean`` (d), ``cov`` (d x d; None without ``cov``), ``quantiles`` (len(quantiles) x d marginal type-7 quantiles over the
+        particles with a positive weight), ``W = sum(Wns)``, ``ess = W^2 / sum(Wns^2)`` and ``n_pos = #(Wns > 0)``; abcdemc has no
+        weights: every particle counts once.  ``corrected``: cov = S / (W - Q / W) instead of S / W.  On the HIP engine a few
+        launches over the packed rows (fixed summation trees, exact order statistics -- bit for bit
+        :func:`abcdez_amd.summary.summary_reference` of the downloaded result) and a few hundred bytes to the host; it changes
+        nothing a continued run depends on.  Engines without the device call get the numpy restatement of their result."""
+        from . import summary as _summary
+
+        probs = tuple(float(p) for p in quantiles)
+        if any(not 0.0 <= p <= 1.0 for p in probs):
+            raise ValueError("summary: p must be in [0, 1]")
+        if not hasattr(self.ops, "posterior_moments"):
+            res = self.result()
+            return _summary.summary_reference(res["P"], res["Wns"] if self.packed else None, cov=cov, corrected=corrected,
+                                              quantiles=probs)
+        self._stream()
+        if self.packed:
+            pop = (self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns)
+        else:
+            pop = (None, self.buf[self.cur][0], None, None)
+        mean, S, W, Q, n_pos = self.ops.posterior_moments(*pop, self.N, want_second=cov)
+        qs = np.empty((len(probs), self.spec.d))
+        if probs:
+            for k in range(self.spec.d):
+                qs[:, k] = self.ops.posterior_quantiles(*pop, self.N, k, probs)
+        return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected)
 
     def _to_host(self, tensors):
         """device tensors -> numpy arrays.  On the GPU: contiguous copies into PINNED host memory, all enqueued back to back on

@@ -102,6 +102,16 @@ def _check(cond: bool, msg: str) -> None:
         raise ValueError(msg)  # the reference raises ErrorException via error(...)
 
 
+def _summary_options(summary, download):
+    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None"""
+    if summary is None or summary is False:
+        _check(bool(download), "download=False needs summary: the result would be empty")
+        return None
+    from .summary import summary_options
+
+    return summary_options(summary)
+
+
 def _make_engine(spec: ModelSpec, nparticles: int, engine, process_group, storage: str = "packed"):
     if engine is not None:
         if not callable(engine):
@@ -121,7 +131,7 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
              nsims_max: int = 10 ** 7, Kmcmc: int = 3, Kmcmc_min: float = 1.0,
              ABCk=IndicatorStrict0toϵ, facc_stop: float = 0.0, facc_min: float = 0.0, facc_tune: float = 0.975,
              verbose: bool = True, verboseout: bool = True, rng: int = 1, parallel: bool = False,
-             engine=None, process_group=None, max_iters: int = 1_000_000, resume=None):
+             engine=None, process_group=None, max_iters: int = 1_000_000, resume=None, summary=None, download: bool = True):
     """Run ABC with differential-evolution moves in an SMC setup (src/abcdez_smc.jl:215).
 
     Same positional arguments, keywords and defaults as the reference, except:
@@ -136,7 +146,13 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     ``checkpoint()`` returns the population and the host loop's variables, and ``resume=<that dict>`` (or the
     path of a file written by :func:`save_checkpoint`) continues the run.  All randomness is counter-based,
     so a resumed run reproduces the uninterrupted one bit for bit.
+
+    Posterior summaries: ``summary=True`` (or a dict of the options ``cov``, ``corrected``, ``quantiles`` of
+    :meth:`PopulationEngine.posterior_summary`) puts weighted mean, covariance, marginal quantiles, ``W``, ``ess`` and
+    ``n_pos`` of the final population into ``r.summary``, computed where the population lives.  ``download=False`` (needs
+    ``summary``) then skips the download of the rows: ``r.P``, ``r.Wns``, ``r.C`` and ``r.blobs`` are None.
     """
+    sum_opts = _summary_options(summary, download)
     # ---- initialisation / validation: src/abcdez_smc.jl:223-235
     _check(0.0 <= α < 1.0, "α must be in 0 <= α < 1")
     _check(0.0 <= δess <= 1.0, "δess must be in 0 <= δess <= 1")
@@ -251,8 +267,12 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     if verbose:                        # smc:379
         log.info("Final run: iteration=%d nsim=%d ϵ=%s range_ϵ=%s ess=%s facc=%s logZ=%s", iters, nsims, ϵ, eng.extrema(), ess, facc, logZ)
 
-    res = eng.result()                 # P is push_p-cast, smc:382
+    res = eng.result() if download else {"P": None, "Wns": None, "C": None}     # P is push_p-cast, smc:382
     out = Result(P=res["P"], Wns=res["Wns"], C=res["C"], ϵ=ϵ, logZ=logZ, blobs=res.get("blobs"))
+    if sum_opts is not None:
+        from .summary import engine_summary
+
+        out.summary = engine_summary(eng, **sum_opts)
     out.eps = ϵ
     out.iters, out.nsims, out.updates = iters, nsims, updates
     out.engine = eng

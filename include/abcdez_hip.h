@@ -424,6 +424,25 @@ ABCDEZ_API int abcdez_mc_generation_sharded_async(abcdez_ctx* ctx, int64_t N, co
 /* T2  push_p over the population (src/abcdez_types.jl:20-23; result P, smc:382, mc:166). */
 ABCDEZ_API int abcdez_push_p(abcdez_ctx* ctx, const double* theta, int64_t N, double* out);
 
+/* R1  Posterior summaries of the result tuple (P, Wns, ...) of src/abcdez_smc.jl:388-393 / (P, ...) of src/abcdez_mc.jl:166-171,
+ *     taken where the population lives: what test/runtests.jl:159-162 extracts as mean(r.P[r.Wns .> 0.0]), and with it
+ *     covariances and credible intervals -- a few numbers per parameter instead of every row.  Arithmetic: abcdez_spec.h,
+ *     "posterior summaries" (fixed tile trees over the positions, no fma, exact order statistics).
+ *     The population: bits / slot0 / slot1 as in the packed entry points above, wns = the weights (device, N doubles);
+ *     bits == NULL: slot0 is a classic row array theta[N][ld] (abcdemc) and slot1 is ignored; wns == NULL: every weight is 1.
+ *     posterior_moments: mean[d] and, if want_second, S[d*d] (row-major, symmetric; else may be NULL) into HOST arrays, and
+ *       W = sum(Wns), Q = sum(Wns.^2), n_pos = #(Wns > 0).  The host normalises: cov = S / (W - Q / W) (corrected) or S / W.
+ *     posterior_quantiles: q_out[n_probs] (HOST) = type-7 quantiles at probs[n_probs] (HOST) of parameter k over the particles with
+ *       Wns > 0.  Unweighted, so refused for the Epanechnikov kernels, whose positive weights differ.
+ *     Both fail when no weight is positive.  Neither touches a select enqueued ahead or any other state the generations keep in
+ *     the context: a run continued after a summary is bit-identical to one without it.                                  */
+ABCDEZ_API int abcdez_posterior_moments(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                        const double* wns, int32_t want_second, double* mean, double* S, double* W, double* Q,
+                                        int64_t* n_pos);
+ABCDEZ_API int abcdez_posterior_quantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0,
+                                          const double* slot1, const double* wns, int32_t k, const double* probs,
+                                          int32_t n_probs, double* q_out);
+
 /* Test hooks: evaluate the spec arithmetic on the device (fn: 0 log, 1 exp, 2 sincos2pi,
  * 3 rint, 4 floor, 5 sqrt, 6 x/y2, 7 table log, 8 table sincos2pi, 9 sqrt_pn, 10 lgamma,
  * 11 log-density of the context's prior factor (int)y2[i] at x[i], src/abcdez_priors.jl:41-45). */

@@ -888,6 +888,39 @@ ABZ_HD double abz_tree_sum_small(const double* x, int p2) { /* p2 = power of two
  * reduced recursively by the same rule.  Missing elements are +0.0.                */
 #define ABZ_TILE 2048
 
+/* ------------------------------------------------------------------ posterior summaries
+ * What a user extracts from a result (test/runtests.jl:159-162: mean(r.P[r.Wns .> 0.0]), and with it covariances and credible
+ * intervals), taken of the population where it lives.  x_ik = push_p (types.jl:20-23) of parameter k < d of the particle at
+ * position i < N, i.e. r.P; w_i = Wns_i (smc:388-393), or 1 for every particle of abcdemc, which has no weights (mc:166-171).
+ * Weights are non-negative; a position COUNTS iff w_i > 0.  T(v) = the tile tree above over the positions i = 0 .. N-1, the
+ * term of a position that does not count being exactly +0.0 (its row is not read: dead rows may hold anything).
+ *   W = T(w),  Q = T(w_i w_i),  n_pos = #{i : w_i > 0}
+ *   mean_k = T(w_i x_ik) / W                                      one rounding for the product, one IEEE division
+ *   S_jk   = T(w_i ((x_ij - mean_j) (x_ik - mean_k))),  j <= k    roundings in this bracket order, no contraction; S_kj = S_jk
+ * The library returns mean, S, W, Q, n_pos; every host normalises in plain double arithmetic:
+ *   cov = S / W              (corrected = false)
+ *   cov = S / (W - Q / W)    (corrected = true, the default; for the uniform weights of the indicator kernels the n - 1
+ *                             estimator over the particles with Wns > 0),      ess = W W / Q.
+ * Marginal quantiles: for parameter k and probability p the type-7 quantile (Julia's default, as at smc:301) of
+ * {x_ik : w_i > 0}: with n = n_pos and v the values in the total order of their IEEE bit patterns (-0.0 below +0.0),
+ *   h = (n - 1) p + 1,  j = clamp(floor(h), 1, max(n - 1, 1)),  g = h - j,  q = v_j + g (v_j+1 - v_j)   (v_2 = v_1 when n = 1).
+ * It is unweighted, so it is defined only where the positive weights are all equal: an indicator ABCk, or abcdemc. */
+ABZ_HD double abz_summary_term1(double w, double x) { return w * x; }
+ABZ_HD double abz_summary_term2(double w, double xj, double mean_j, double xk, double mean_k) {
+  return w * ((xj - mean_j) * (xk - mean_k));
+}
+ABZ_HD double abz_summary_cov_denominator(double W, double Q, int corrected) { return corrected ? W - Q / W : W; }
+ABZ_HD double abz_quantile_type7(double vj, double vj1, double g) { return vj + g * (vj1 - vj); }
+/* 1-based index j of the lower order statistic and the weight g of the upper one */
+ABZ_HD int64_t abz_quantile_type7_index(int64_t n, double p, double* g) {
+  const double h = (double)(n - 1) * p + 1.0;
+  int64_t j = (int64_t)abz_floor(h);
+  if (j < 1) j = 1;
+  if (j > n - 1) j = n - 1 > 1 ? n - 1 : 1;
+  *g = h - (double)j;
+  return j;
+}
+
 /* ------------------------------------------------------------------ model descriptor
  * What the reference passes as (prior, dist!, varexternal, rng) (smc:215, mc:102).
  * An arbitrary Julia closure cannot run on the device, so dist! is one of the

@@ -489,12 +489,43 @@ function download(e; packed::Bool)
     end
 end
 
+# ---- posterior summaries where the population lives (include/abcdez_spec.h "posterior summaries"): what test/runtests.jl:159-162
+# extracts as mean(r.P[r.Wns .> 0.0]), with covariance and marginal type-7 quantiles -- a few numbers per parameter instead of
+# every row.  packed = true: the abcdesmc population with its weights; packed = false: abcdemc's rows, every particle counts once.
+# cov = S / (W - Q / W) (corrected) or S / W, in plain Float64 arithmetic as every host of the library does it.
+function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, corrected::Bool=true, quantiles=Float64[])
+    # added with library version 620; MIN_VERSION stays where it is, so the calls are probed for
+    ccall((:abcdez_version, LIB), Cint, ()) >= 620 || error("ABCdeZHIP: posterior_summary needs libabcdez_hip.so version 620 or later (rebuild the library)")
+    bits = packed ? e.bits[e.bc] : C_NULL; s0 = packed ? e.slot[1] : e.slot[e.cur]; s1 = packed ? e.slot[2] : C_NULL
+    w = packed ? e.wns : C_NULL
+    mean = Vector{Float64}(undef, e.d); S = Matrix{Float64}(undef, e.d, e.d)
+    W = Ref(0.0); Q = Ref(0.0); npos = Ref(Int64(0))
+    check(ccall((:abcdez_posterior_moments, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Float64}, Ref{Int64}),
+                e.ctx, bits, e.N, s0, s1, w, cov ? 1 : 0, mean, S, W, Q, npos))
+    probs = collect(Float64, quantiles); q = Vector{Float64}(undef, length(probs)); qs = Matrix{Float64}(undef, length(probs), e.d)
+    for k in 1:(isempty(probs) ? 0 : e.d)                   # one column gather + one exact rank select per probability
+        check(ccall((:abcdez_posterior_quantiles, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}),
+                    e.ctx, bits, e.N, s0, s1, w, k - 1, probs, length(probs), q))
+        qs[:, k] = q
+    end
+    den = corrected ? W[] - Q[] / W[] : W[]
+    (mean = mean, cov = cov ? S ./ den : nothing, quantiles = qs, W = W[], ess = W[] * W[] / Q[], n_pos = Int(npos[]))
+end
+# the drivers' `summary` keyword: true, or a NamedTuple of the options above, e.g. (quantiles = [0.025, 0.975],)
+summary_of(e, summary; packed::Bool) = summary === nothing ? nothing :
+    posterior_summary(e; packed = packed, (summary === true ? NamedTuple() : summary)...)
+
 # ---- abcdesmc!: the host loop of src/abcdez_smc.jl:215-394, each ★ call replaced by one ccall ----
 function abcdesmc!(prior, dist!::DeviceSimulator, ϵ_target, varexternal;
                    nparticles::Int=100, α=0.95, δess=0.5, nsims_max::Int=10^7, Kmcmc::Int=3, Kmcmc_min=1.0,
                    ABCk=ABCdeZ.IndicatorStrict0toϵ, facc_stop=0.0, facc_min=0.0, facc_tune=0.975,
                    verbose::Bool=true, verboseout::Bool=true, rng::Union{Integer,AbstractRNG}=Random.default_rng(),
-                   parallel::Bool=false, comm=nothing)
+                   parallel::Bool=false, comm=nothing, summary=nothing, download::Bool=true)
+    # summary = true or a NamedTuple of posterior_summary's options: the result carries `summary`; download = false (needs summary)
+    # leaves the rows on the device: P, Wns, C and blobs are `nothing`
+    (download || summary !== nothing) || error("download=false needs summary: the result would be empty")
     # comm = (id, rank, world): one of `world` processes, one GPU each (top of this file); every rank must pass the same integer `rng`
     # `varexternal` and `parallel` are accepted and ignored: the device simulator holds its own data (no per-task deepcopy,
     # smc:166-173) and the whole population always runs in parallel on the GPU (smc:237's executor has no counterpart)
@@ -561,10 +592,12 @@ function abcdesmc!(prior, dist!::DeviceSimulator, ϵ_target, varexternal;
         check(ccall((:abcdez_smc_select_discard, LIB), Cint, (Ptr{Cvoid},), e.ctx))        # the run ends: nothing is left armed
         push!(ranges_ϵ, extrema_dev(e))                                                     # smc:364 of the last generation
         verbose && (@info "Final run:" iteration = iters nsim = nsims ϵ = ϵ range_ϵ = ranges_ϵ[end] ess = ess facc = facc logZ = logZ)   # smc:379
-        P, Wns, Δs, blobs = download(e; packed=true)                                        # smc:382
-        return verboseout ? (P = P, Wns = Wns, C = Δs, ϵ = ϵ, logZ = logZ, blobs = blobs, ϵs = ϵs, ranges_ϵ = ranges_ϵ,
-                             logZs = logZs, esss = esss, faccs = faccs, γ0s = γ0s, Kmcmcs = Kmcmcs) :
-                            (P = P, Wns = Wns, C = Δs, ϵ = ϵ, logZ = logZ, blobs = blobs)  # smc:388-393
+        sm = summary_of(e, summary; packed=true)
+        P, Wns, Δs, blobs = download ? ABCdeZHIP.download(e; packed=true) : (nothing, nothing, nothing, nothing)   # smc:382
+        res = verboseout ? (P = P, Wns = Wns, C = Δs, ϵ = ϵ, logZ = logZ, blobs = blobs, ϵs = ϵs, ranges_ϵ = ranges_ϵ,
+                            logZs = logZs, esss = esss, faccs = faccs, γ0s = γ0s, Kmcmcs = Kmcmcs) :
+                           (P = P, Wns = Wns, C = Δs, ϵ = ϵ, logZ = logZ, blobs = blobs)   # smc:388-393
+        return sm === nothing ? res : merge(res, (summary = sm,))
     finally
         free!(e)
     end
@@ -624,7 +657,8 @@ end
 
 function abcdemc!(prior, dist!::DeviceSimulator, ϵ_target, varexternal;
                   nparticles::Int=50, generations::Int=20, verbose=true, rng::Union{Integer,AbstractRNG}=Random.default_rng(),
-                  parallel::Bool=false, comm=nothing)
+                  parallel::Bool=false, comm=nothing, summary=nothing, download::Bool=true)
+    (download || summary !== nothing) || error("download=false needs summary: the result would be empty")   # as in abcdesmc!
     # comm = (id, rank, world): one of `world` processes, one GPU each (top of this file); every rank must pass the same integer `rng`
     (comm === nothing || rng isa Integer) || error("comm: a sharded run needs the same integer rng on every rank")
     α = 0.0                                                                              # mc:107
@@ -658,8 +692,10 @@ function abcdemc!(prior, dist!::DeviceSimulator, ϵ_target, varexternal;
         while !isempty(tickets); collect!(); end
         conv = ϵ_h <= ϵ_target                                                               # mc:163
         verbose && (@info "End:" completion = complete converged = conv nsim = nsims range_ϵ = (ϵ_l, ϵ_h))   # mc:164
-        P, _, Δs, blobs = download(e; packed=false)                                          # mc:166
-        return (P = P, C = Δs, reached_ϵ = conv, blobs = blobs)                              # mc:171
+        sm = summary_of(e, summary; packed=false)
+        P, _, Δs, blobs = download ? ABCdeZHIP.download(e; packed=false) : (nothing, nothing, nothing, nothing)   # mc:166
+        res = (P = P, C = Δs, reached_ϵ = conv, blobs = blobs)                               # mc:171
+        return sm === nothing ? res : merge(res, (summary = sm,))
     finally
         free!(e)
     end
