@@ -2,6 +2,7 @@
 (abcdez_amd/summary.py; include/abcdez_spec.h, "posterior summaries") against the CPU oracle's tile tree and against numpy's own
 weighted mean / covariance / quantile, and the drivers' ``summary`` / ``download`` keywords through the oracle engine."""
 import math
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -117,6 +118,147 @@ def test_reference_refusals():
     with pytest.raises(ValueError, match=r"p must be in \[0, 1\]"):
         summary_reference(X, None, quantiles=(1.5,))
     assert summary_reference(X, np.arange(10.0)).mean[0] == pytest.approx(np.average(X, weights=np.arange(10.0)))
+
+
+def yardstick_population():
+    """(X, w) for the exact-arithmetic yardstick: N = 5001 (three tiles, the last ragged), d = 2, about 30 % of the positions dead,
+    unequal weights; column 0 = 1e8 + 1e-3 normal -- a one-pass sum(w x^2) - W mean^2 loses every digit of its variance (1e-6
+    against terms of 1e16), and so does a centring by a mean that is off by more than its own rounding -- column 1 = a standard
+    normal.  The dead rows are left finite here; the callers overwrite them."""
+    rng = np.random.default_rng(20260)
+    N = 5001
+    X = np.stack([1e8 + 1e-3 * rng.standard_normal(N), rng.standard_normal(N)], axis=1)
+    w = rng.random(N)
+    w[rng.random(N) < 0.3] = 0.0
+    return X, w
+
+
+def exact_yardstick(X, w, s):
+    """The record ``s`` (mean, S, W of :func:`summary_reference` or of the device) against exact rational arithmetic on the
+    rows X and weights w.  Returns [(what, |error|, bound)] with error and bound as exact Fractions.
+
+    The bounds are derived (first order in u = 2^-53, the +6 / +2 left over paying for every higher-order term), not measured.
+    L = 11 + ceil(log2(#tiles)) is the number of additions a term passes through on its way to the root of the tile tree: 3 inside
+    a slot's eight terms, 8 over the 256 slots of a tile, and the same pairing over the tile partials above.  A sum of n terms
+    along a tree of depth L has an error of at most L u sum|term| (every addition rounds a partial sum whose magnitude is at most
+    sum|term| of its leaves, and a leaf lies under L additions).
+      mean_k = fl(T(fl(w x_k)) / T(w)).  Numerator: one rounding per product + the tree, (L + 1) u sum|w x_k|.  Denominator: the
+        weights are exact and positive, L u W.  Carried through the quotient, plus the division's own rounding u |mean_k|, and with
+        |mean_k| W <= sum|w x_k|:  |mean_k - exact| <= ((L + 1) + L + 1) u sum|w x_k| / W = (2 L + 2) u ...  <= (2 L + 6) u sum|w x_k| / W.
+      S_jk = T(fl(w fl(fl(x_j - m_j) fl(x_k - m_k)))) with m the COMPUTED mean taken as exact rationals (the statistic is defined
+        around the mean the call returns): two subtractions, two products, 4 u relative per term, + L u for the tree:
+        |S_jk - exact| <= (L + 4) u sum|w c_j c_k| <= (L + 6) u sum|w c_j c_k|,  c = x - m exactly.
+    (No product here comes near the subnormal range, where a rounding is no longer relative.)"""
+    F = Fraction
+    X = np.asarray(X, dtype=np.float64)
+    N, d = X.shape
+    live = np.flatnonzero(np.asarray(w) > 0.0)
+    L = 11 + math.ceil(math.log2(-(-N // 2048))) if N > 2048 else 11
+    u = F(1, 2 ** 53)
+    wl = [F(float(w[i])) for i in live]
+    xl = [[F(float(X[i, k])) for i in live] for k in range(d)]
+    W = sum(wl)
+    out = [("W", abs(F(float(s.W)) - W), L * u * W)]
+    for k in range(d):
+        exact = sum(a * b for a, b in zip(wl, xl[k])) / W
+        out.append((f"mean[{k}]", abs(F(float(s.mean[k])) - exact), (2 * L + 6) * u * sum(abs(a * b) for a, b in zip(wl, xl[k])) / W))
+    m = [F(float(v)) for v in s.mean]
+    c = [[x - m[k] for x in xl[k]] for k in range(d)]
+    for j in range(d):
+        for k in range(j, d):
+            terms = [a * cj * ck for a, cj, ck in zip(wl, c[j], c[k])]
+            out.append((f"S[{j},{k}]", abs(F(float(s.S[j, k])) - sum(terms)), (L + 6) * u * sum(abs(t) for t in terms)))
+    return out
+
+
+def test_reference_meets_derived_bounds_against_exact_arithmetic():
+    """the centred two-pass second moment of the restatement against Fractions, on an input a one-pass formula cannot survive"""
+    X, w = yardstick_population()
+    live = w > 0.0
+    assert 0.25 < 1.0 - live.mean() < 0.35 and np.unique(w[live]).size > 3000
+    Xn = X.copy()
+    Xn[~live] = np.nan
+    s = summary_reference(Xn, w)
+    worst = 0.0
+    for what, err, bound in exact_yardstick(X, w, s):
+        print(what, float(err), float(bound), float(err / bound))
+        assert err <= bound, what
+        worst = max(worst, float(err / bound))
+    print("worst error / bound", worst)
+    # the input has teeth: the one-pass variance of column 0, in the same double arithmetic, misses the same bound by far
+    x0, wl = X[live, 0], w[live]
+    one_pass = math.fsum(wl * x0 * x0) - s.W * s.mean[0] * s.mean[0]
+    m0 = Fraction(float(s.mean[0]))
+    terms = [Fraction(float(a)) * (Fraction(float(b)) - m0) ** 2 for a, b in zip(wl, x0)]
+    assert abs(Fraction(one_pass) - sum(terms)) > 10 ** 6 * (13 + 6) * Fraction(1, 2 ** 53) * sum(terms)
+    assert np.array_equal(s.S, s.S.T)
+
+
+def test_reference_with_a_single_positive_weight():
+    """n_pos = 1, the live position the last of a ragged tile: the mean is the row, S is identically zero (the centred row is
+    zero), the corrected denominator W - Q / W is 0 and cov = 0 / 0, and every quantile equals the row.
+    A -0.0 component comes out as +0.0, in the mean (-0.0 plus the +0.0 terms of the other positions) and in the quantile: the
+    order statistic is -0.0, but the type-7 formula of the spec, v_j + g (v_j+1 - v_j) with v_j+1 = v_j, is -0.0 + g * (+0.0) =
+    +0.0 in IEEE arithmetic for every g >= 0 -- as in Julia's quantile, whose formula this is (smc:301).  Pinned here so that the
+    device, which is compared with this restatement bit for bit, cannot drift either way."""
+    N = 4099
+    row = np.array([1.5, -0.0, -2.25e-300])
+    X = np.full((N, 3), np.nan)
+    X[1::2] = np.inf
+    X[2::3] = -np.inf
+    X[N - 1] = row
+    w = np.zeros(N)
+    w[N - 1] = 1.0
+    with np.errstate(invalid="ignore"):
+        s = summary_reference(X, w, quantiles=(0.0, 0.3, 0.5, 1.0))
+    assert s.n_pos == 1 and s.W == 1.0 and s.Q == 1.0 and s.ess == 1.0
+    assert np.array_equal(s.mean, row) and not np.signbit(s.mean[1])                # +0.0 terms of the dead positions: -0.0 + 0.0
+    assert np.array_equal(s.S, np.zeros((3, 3))) and np.isnan(s.cov).all()
+    assert s.quantiles.shape == (4, 3)
+    for i in range(4):
+        assert np.array_equal(s.quantiles[i], row)
+        assert s.quantiles[i, [0, 2]].tobytes() == row[[0, 2]].tobytes() and not np.signbit(s.quantiles[i, 1])
+    unc = summary_reference(X, w, corrected=False)
+    assert np.array_equal(unc.cov, np.zeros((3, 3)))
+
+
+def test_reference_with_two_positive_weights_in_different_tiles():
+    """n_pos = 2 at positions 0 and 2048; values on which every operation is exact, so the results are asserted directly"""
+    N = 4099
+    X = np.full((N, 2), np.nan)
+    X[1:2048] = np.inf
+    X[0] = (1.0, -4.0)
+    X[2048] = (3.0, 8.0)
+    w = np.zeros(N)
+    w[[0, 2048]] = 0.5
+    s = summary_reference(X, w, quantiles=(0.0, 0.3, 0.5, 1.0))
+    assert s.n_pos == 2 and s.W == 1.0 and s.Q == 0.5 and s.ess == 2.0
+    assert list(s.mean) == [2.0, 2.0]
+    assert s.S.tolist() == [[1.0, 6.0], [6.0, 36.0]]                               # 0.5 ((-1)(-1) + 1 1), 0.5 ((-1)(-6) + 1 6), ...
+    assert s.cov.tolist() == [[2.0, 12.0], [12.0, 72.0]]                           # / (W - Q / W) = 0.5: the n - 1 estimator
+    g = (0.3 + 1.0) - 1.0                                                          # h = (n - 1) p + 1, j = 1, g = h - 1: not 0.3
+    assert s.quantiles[:, 0].tolist() == [1.0, 1.0 + g * 2.0, 2.0, 3.0]            # v1 + g (v2 - v1)
+    assert s.quantiles[:, 1].tolist() == [-4.0, -4.0 + g * 12.0, 2.0, 8.0]
+
+
+def test_reference_never_reads_a_dead_row_or_a_weight_that_does_not_count():
+    """NaN / +-inf in the rows of dead positions, and weights of -0.0, -1.0, NaN and +0.0 between live ones: the result is that
+    of the live rows alone"""
+    rng = np.random.default_rng(77)
+    N = 2 * 2048 + 77
+    X = rng.standard_normal((N, 3))
+    w = np.full(N, 1.0 / N)
+    dead = rng.permutation(N)[:N // 2]
+    w[dead] = np.resize(np.array([-0.0, -1.0, np.nan, 0.0]), dead.size)
+    clean = summary_reference(np.where((w > 0)[:, None], X, 0.0), np.where(w > 0, w, 0.0), quantiles=PROBS)
+    X[dead] = np.resize(np.array([np.nan, np.inf, -np.inf]), (dead.size, 3))
+    s = summary_reference(X, w, quantiles=PROBS)
+    assert s.n_pos == N - N // 2 == clean.n_pos and s.W == clean.W and s.Q == clean.Q
+    for f in ("mean", "S", "cov", "quantiles"):
+        assert np.isfinite(getattr(s, f)).all() and getattr(s, f).tobytes() == getattr(clean, f).tobytes(), f
+    live = w > 0
+    assert abs(s.mean[0] - X[live, 0].mean()) <= 64 * U * np.abs(X[live, 0]).mean()
+    assert s.quantiles[0, 1] == X[live, 1].min() and s.quantiles[-1, 1] == X[live, 1].max()
 
 
 PRIOR, SIM = A.Normal(0, math.sqrt(10)), A.Normal1D(3.0)
