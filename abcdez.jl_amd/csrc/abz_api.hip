@@ -104,10 +104,10 @@ extern "C" {
 
 /* 400: Philox4x32-10 again, abz_model.mv, group abort; 401: abcdemc's better particle by rejection;
  * 500: abcdez_comm_* and abcdez_smc_sweeps_sharded (RCCL behind the ABI), timing mode 3; 600: abcdez_comm_init_host (a host-supplied
- * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles.  Hosts refuse a library older than the
+ * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles.  Hosts refuse a library older than the
  * header they were written against (abcdez.jl_amd/_lib.py, julia/ABCdeZHIP.jl check_abi): a signature that grew an argument links
  * against an old binary without a diagnostic. */
-int abcdez_version(void) { return 620; }
+int abcdez_version(void) { return 630; }
 int abcdez_rng_rounds(void) { return ABZ_PHILOX_ROUNDS; }
 
 /* sizeof / offsetof of the two structs that cross the boundary, so that a host that mirrors them by hand (the Julia
@@ -1490,6 +1490,22 @@ int abcdez_posterior_quantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N,
               "posterior_quantiles: weighted quantiles are not provided (the Epanechnikov kernels give unequal weights; "
               "mean and covariance work for every kernel)");
   return abz_posterior_quantiles_impl(ctx, bits, N, slot0, slot1, wns, k, probs, n_probs, q_out);
+}
+
+/* Weighted marginal quantiles over the integer masses of the resampler (csrc/abz_wquantile.hip): every ABC kernel, with or
+ * without a weight array; like its neighbours it only reads the population. */
+int abcdez_posterior_wquantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                const double* wns, int32_t k0, int32_t nk, const double* probs, int32_t n_probs, double* q_out,
+                                uint64_t* M, int64_t* n_mass) {
+  ABZ_REQUIRE(ctx && slot0 && probs && q_out && M && n_mass, "posterior_wquantiles: null argument");
+  ABZ_REQUIRE(!bits || slot1, "posterior_wquantiles: packed storage (bits) needs both row slots");
+  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_wquantiles: N out of range");
+  ABZ_REQUIRE(nk >= 1 && k0 >= 0 && (int64_t)k0 + (int64_t)nk <= (int64_t)ctx->h_model.d,
+              "posterior_wquantiles: the columns must be 0 <= k0, nk >= 1, k0 + nk <= length(prior)");
+  ABZ_REQUIRE(n_probs >= 1, "posterior_wquantiles: n_probs must be at least 1");
+  for (int32_t q = 0; q < n_probs; ++q)
+    ABZ_REQUIRE(probs[q] >= 0.0 && probs[q] <= 1.0, "posterior_wquantiles: p must be in [0, 1]");
+  return abz_posterior_wquantiles_impl(ctx, bits, N, slot0, slot1, wns, k0, nk, probs, n_probs, q_out, M, n_mass);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

@@ -339,6 +339,8 @@ int abz_posterior_moments_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, con
                                int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
 int abz_posterior_quantiles_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
                                  int k, const double* probs, int n_probs, double* q_out);
+int abz_posterior_wquantiles_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                                  int k0, int nk, const double* probs, int n_probs, double* q_out, uint64_t* M, int64_t* n_mass);
 void abz_fold_counters(abcdez_ctx*);
 /* Read-back of the first `nwords` device scalars WITHOUT the copy engine and without a stream synchronisation: a one-block
  * kernel writes them straight into the pinned host mirror and stores a sequence word last (system-scope release); the

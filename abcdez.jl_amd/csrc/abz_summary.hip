@@ -23,21 +23,13 @@
 
 #include "abz_ctx.h"
 #include "abz_device.h"
+#include "abz_summary.h"
 
 int abz_select_impl(abcdez_ctx*, const double*, const uint8_t*, int64_t, int64_t, double*, double*, int64_t*);
 
 #define ABZ_SUM_CB 8        /* first pass: columns per thread and trip */
 #define ABZ_SUM_JB 4        /* second pass: columns j held per thread */
 #define ABZ_SUM_KC 4        /* second pass: columns k streamed per trip */
-
-struct SumPop {
-  const uint32_t* bits;     /* NULL: classic storage, slot0 is the row array */
-  const double* slot0;
-  const double* slot1;
-  const double* wns;        /* NULL: unit weights */
-  int64_t N;
-  int ld, d;
-};
 
 /* the 8 positions of thread t in its tile: weight (0.0 where the position does not count or lies past N) and current row
  * (NULL there: never read) */
@@ -242,7 +234,7 @@ __global__ __launch_bounds__(ABZ_BLOCK) void sum_column_kernel(const abz_model* 
 }
 
 /* ================================================================ host side */
-static int sum_ws_reserve(abcdez_ctx* ctx, size_t bytes) {
+int sum_ws_reserve(abcdez_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->sum_ws_bytes) return 0;
   ABZ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (ctx->sum_ws) ABZ_HIP_CHECK(hipFree(ctx->sum_ws));
@@ -252,13 +244,6 @@ static int sum_ws_reserve(abcdez_ctx* ctx, size_t bytes) {
   ctx->sum_ws_bytes = want;
   return 0;
 }
-static SumPop sum_pop(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns) {
-  SumPop p{};
-  p.bits = bits; p.slot0 = slot0; p.slot1 = bits ? slot1 : slot0; p.wns = wns; p.N = N;
-  p.ld = ctx->h_model.ld; p.d = ctx->h_model.d;
-  return p;
-}
-
 int abz_posterior_moments_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
                                const double* wns, int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos) {
   const int d = ctx->h_model.d;

@@ -457,10 +457,10 @@ class HipOps:
         _lib.check(self.lib, self.lib.abcdez_sync(self.ctx))
 
     # ---- blobs: stamps carried with the distances, simulated data rebuilt on demand (include/abcdez_hip.h) ----
-    def _summary_fn(self, name):
+    def _summary_fn(self, name, since=620):
         fn = getattr(self.lib, name, None)
-        if fn is None or fn.argtypes is None:       # a library older than 620 (_lib.OPTIONAL_SYMBOLS): no quiet fall-back
-            raise _lib.AbcdezError(f"{_lib.LIB_PATH} does not export {name} (abcdez_version() = {self.lib.abcdez_version()} < 620): "
+        if fn is None or fn.argtypes is None:       # a library older than `since` (_lib.OPTIONAL_SYMBOLS): no quiet fall-back
+            raise _lib.AbcdezError(f"{_lib.LIB_PATH} does not export {name} (abcdez_version() = {self.lib.abcdez_version()} < {since}): "
                                    "rebuild it (`make -C abcdez.jl_amd/csrc`)")
         return fn
 
@@ -483,6 +483,18 @@ class HipOps:
         _lib.check(self.lib, self._summary_fn("abcdez_posterior_quantiles")(
             self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), int(k), p.ctypes.data, int(p.size), q.ctypes.data))
         return q
+
+    def posterior_wquantiles(self, bits, slot0, slot1, wns, N, probs, k0=0, nk=None):
+        """(q[nk, len(probs)], M, n_mass): weighted quantiles at ``probs`` of the parameters k0 .. k0 + nk - 1 (default: all from k0)
+        over the integer masses of the resampler, one library call and one read-back (abcdez_posterior_wquantiles)"""
+        nk = self.spec.d - int(k0) if nk is None else int(nk)
+        p = np.ascontiguousarray(probs, dtype=np.float64)
+        q = np.empty((max(nk, 0), p.size), dtype=np.float64)
+        M, n_mass = C.c_uint64(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn("abcdez_posterior_wquantiles", 630)(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), int(k0), nk, p.ctypes.data, int(p.size), q.ctypes.data,
+            C.byref(M), C.byref(n_mass)))
+        return q, M.value, n_mass.value
 
     def set_stamps(self, cur, nxt):
         _lib.check(self.lib, self.lib.abcdez_ctx_set_stamps(self.ctx, _ptr(cur), _ptr(nxt)))
@@ -1267,23 +1279,29 @@ class PopulationEngine:
         w = self.wns
         return ((w[:, None] * th).sum(dim=0) / w.sum()).cpu().numpy()
 
-    def posterior_summary(self, cov: bool = True, corrected: bool = True, quantiles=()):
+    def posterior_summary(self, cov: bool = True, corrected: bool = True, quantiles=(), wquantiles=()):
         """Posterior summaries of the population where it lives (include/abcdez_spec.h, "posterior summaries"): a record with
         ``mean`` (d), ``cov`` (d x d; None without ``cov``), ``quantiles`` (len(quantiles) x d marginal type-7 quantiles over the
         particles with a positive weight), ``W = sum(Wns)``, ``ess = W^2 / sum(Wns^2)`` and ``n_pos = #(Wns > 0)``; abcdemc has no
         weights: every particle counts once.  ``corrected``: cov = S / (W - Q / W) instead of S / W.  On the HIP engine a few
         launches over the packed rows (fixed summation trees, exact order statistics -- bit for bit
         :func:`abcdez_amd.summary.summary_reference` of the downloaded result) and a few hundred bytes to the host; it changes
-        nothing a continued run depends on.  Engines without the device call get the numpy restatement of their result."""
+        nothing a continued run depends on.  Engines without the device call get the numpy restatement of their result.
+
+        ``wquantiles``: probabilities of the WEIGHTED marginal quantiles (include/abcdez_spec.h, "weighted quantiles"), for every
+        ABC kernel -- the Epanechnikov kernels' unequal weights included, where ``quantiles`` is refused.  They come back as
+        ``wquantiles`` (len(wquantiles) x d) with the total integer mass ``M`` and ``n_mass``, the number of positions that carry
+        mass; one library call and one read-back serve all columns and probabilities."""
         from . import summary as _summary
 
         probs = tuple(float(p) for p in quantiles)
-        if any(not 0.0 <= p <= 1.0 for p in probs):
+        wprobs = tuple(float(p) for p in wquantiles)
+        if any(not 0.0 <= p <= 1.0 for p in probs + wprobs):
             raise ValueError("summary: p must be in [0, 1]")
         if not hasattr(self.ops, "posterior_moments"):
             res = self.result()
             return _summary.summary_reference(res["P"], res["Wns"] if self.packed else None, cov=cov, corrected=corrected,
-                                              quantiles=probs)
+                                              quantiles=probs, wquantiles=wprobs)
         self._stream()
         if self.packed:
             pop = (self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns)
@@ -1294,7 +1312,11 @@ class PopulationEngine:
         if probs:
             for k in range(self.spec.d):
                 qs[:, k] = self.ops.posterior_quantiles(*pop, self.N, k, probs)
-        return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected)
+        wq = M = n_mass = None
+        if wprobs:
+            q, M, n_mass = self.ops.posterior_wquantiles(*pop, self.N, wprobs)
+            wq = np.ascontiguousarray(q.T)
+        return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass)
 
     def _to_host(self, tensors):
         """device tensors -> numpy arrays.  On the GPU: contiguous copies into PINNED host memory, all enqueued back to back on

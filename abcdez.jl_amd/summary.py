@@ -66,19 +66,96 @@ def cov_denominator(W: float, Q: float, corrected: bool) -> float:
     return W - Q / W if corrected else W
 
 
-def make_summary(mean, S, W, Q, n_pos, quantiles, probs, corrected=True):
+def make_summary(mean, S, W, Q, n_pos, quantiles, probs, corrected=True, wquantiles=None, wprobs=(), M=None, n_mass=None):
     """the record ``posterior_summary`` returns, from what the library (or the restatement below) computes"""
     W, Q = float(W), float(Q)
     cov = None if S is None else np.asarray(S, dtype=np.float64) / cov_denominator(W, Q, corrected)
+    if wquantiles is None:
+        wquantiles = np.empty((0, np.asarray(mean).shape[0]))
     return SimpleNamespace(mean=np.asarray(mean, dtype=np.float64), cov=cov, S=S, W=W, Q=Q, ess=W * W / Q, n_pos=int(n_pos),
-                           quantiles=quantiles, probs=tuple(probs), corrected=bool(corrected))
+                           quantiles=quantiles, probs=tuple(probs), corrected=bool(corrected), wquantiles=wquantiles,
+                           wprobs=tuple(wprobs), M=None if M is None else int(M), n_mass=None if n_mass is None else int(n_mass))
 
 
-def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=()):
+def stratum_bits(n: int) -> int:
+    """abz_stratum_bits: fraction bits of the resampler's fixed point, 40 up to 2^23 positions"""
+    lg = 0
+    while lg < 32 and (1 << lg) < n:
+        lg += 1
+    return 40 if lg <= 23 else 63 - lg
+
+
+def weight_fix(w, n: int):
+    """abz_weight_fix of every weight: rint(w n 2^b) as Python integers (a list); zero, negative and NaN weights carry no mass,
+    the result saturates at 2^63"""
+    b = stratum_bits(n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.asarray(w, dtype=np.float64) * float(n) * (2.0 ** b)
+    out = []
+    for x in v.tolist():
+        if not x > 0.0:
+            out.append(0)
+        elif x >= 2.0 ** 63:
+            out.append(1 << 63)
+        else:
+            out.append(int(np.rint(x)))
+    return out
+
+
+def wquantile_column(values, masses, probs):
+    """The weighted quantile of include/abcdez_spec.h ("posterior summaries", weighted quantiles) of ONE column, literally:
+    ``values`` and ``masses`` (Python integers >= 1) of the counting positions; sort by (order key, mass), integer partial sums."""
+    keys = order_keys(values).tolist()
+    order = sorted(range(len(keys)), key=lambda i: (keys[i], masses[i]))
+    v = [float(values[i]) for i in order]
+    m = [masses[i] for i in order]
+    n = len(v)
+    cum, s = [], 0
+    for x in m:
+        s += x
+        cum.append(s)                                   # S_1 .. S_n
+    M = s
+    import bisect
+    out = []
+    for p in probs:
+        span = M - m[0]
+        t = min(int(math.floor(p * float(span))), span)
+        H = m[0] + t
+        k = bisect.bisect_right(cum, H)                 # 0-based index of the smallest S_k > H
+        if n == 1 or k >= n:
+            out.append(v[n - 1])
+            continue
+        assert k >= 1
+        g = float(H - cum[k - 1]) / float(m[k])
+        out.append(float(np.float64(v[k - 1]) + np.float64(g) * (np.float64(v[k]) - np.float64(v[k - 1]))))
+    return out
+
+
+def wquantiles_reference(X, w, probs):
+    """(wquantiles (len(probs) x d), M, n_mass) of the population X (N x d) with the weights w (None: every position has the
+    mass 2^b); refuses like the library"""
+    N, d = X.shape
+    masses = [1 << stratum_bits(N)] * N if w is None else weight_fix(w, N)
+    idx = [i for i in range(N) if masses[i] >= 1]
+    if not idx:
+        raise ValueError("summary: no particle has a positive weight that carries mass")
+    M = sum(masses)
+    if M >= 1 << 63:
+        raise ValueError("summary: the total mass reaches 2^63 -- the weights are not normalised")
+    ml = [masses[i] for i in idx]
+    out = np.empty((len(probs), d))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(d):
+            out[:, k] = wquantile_column(X[idx, k], ml, probs)
+    return out, M, len(idx)
+
+
+def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquantiles=()):
     """numpy restatement of the summary arithmetic.  ``P``: the push_p-cast population, shape (N,) or (N, d) (``r.P``);
     ``Wns``: the weights (``r.Wns``), or None for unit weights (abcdemc).  Returns the record of :func:`make_summary`:
     ``mean`` (d), ``cov`` (d x d, or None), ``S`` (the unnormalised second central moments), ``quantiles``
-    (len(quantiles) x d), ``W``, ``Q``, ``ess = W^2 / Q``, ``n_pos``."""
+    (len(quantiles) x d), ``W``, ``Q``, ``ess = W^2 / Q``, ``n_pos``, and for ``wquantiles`` the weighted quantiles ``wquantiles``
+    (len(wquantiles) x d) with the total integer mass ``M`` and ``n_mass`` (both None when none are asked for)."""
     X = np.asarray(P, dtype=np.float64)
     if X.ndim == 1:
         X = X[:, None]
@@ -87,7 +164,8 @@ def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=()):
     if w.shape != (N,):
         raise ValueError("summary: one weight per particle expected")
     probs = tuple(float(p) for p in quantiles)
-    if any(not 0.0 <= p <= 1.0 for p in probs):
+    wprobs = tuple(float(p) for p in wquantiles)
+    if any(not 0.0 <= p <= 1.0 for p in probs + wprobs):
         raise ValueError("summary: p must be in [0, 1]")
     live = w > 0.0
     n_pos = int(live.sum())
@@ -119,19 +197,22 @@ def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=()):
                 a = vals[j - 1]
                 b = vals[j] if n_pos > 1 else a
                 qs[i, k] = a + g * (b - a)
-    return make_summary(mean, S, W, Q, n_pos, qs, probs, corrected)
+    wq = M = n_mass = None
+    if wprobs:
+        wq, M, n_mass = wquantiles_reference(X, None if Wns is None else w, wprobs)
+    return make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass)
 
 
 def summary_options(summary) -> dict:
-    """the ``summary=`` keyword of the drivers: True, or a dict of cov / corrected / quantiles"""
+    """the ``summary=`` keyword of the drivers: True, or a dict of cov / corrected / quantiles / wquantiles"""
     if summary is True:
         return {}
     if isinstance(summary, dict):
-        bad = set(summary) - {"cov", "corrected", "quantiles"}
+        bad = set(summary) - {"cov", "corrected", "quantiles", "wquantiles"}
         if bad:
-            raise ValueError(f"summary: unknown option(s) {sorted(bad)} (cov, corrected, quantiles)")
+            raise ValueError(f"summary: unknown option(s) {sorted(bad)} (cov, corrected, quantiles, wquantiles)")
         return dict(summary)
-    raise ValueError("summary must be None, True or a dict of the options cov, corrected, quantiles")
+    raise ValueError("summary must be None, True or a dict of the options cov, corrected, quantiles, wquantiles")
 
 
 def engine_summary(eng, **opts):

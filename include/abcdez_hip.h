@@ -442,6 +442,16 @@ ABCDEZ_API int abcdez_posterior_moments(abcdez_ctx* ctx, const uint32_t* bits, i
 ABCDEZ_API int abcdez_posterior_quantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0,
                                           const double* slot1, const double* wns, int32_t k, const double* probs,
                                           int32_t n_probs, double* q_out);
+/*     posterior_wquantiles (library version 630): the WEIGHTED marginal quantiles of abcdez_spec.h ("posterior summaries", weighted
+ *       quantiles) of the parameters k0 .. k0 + nk - 1 at probs[n_probs] (HOST), for every ABC kernel and for wns == NULL (every
+ *       position then has the mass 2^b, w_i = 1 / N).  A position counts iff its integer mass abz_weight_fix(w_i, N) is at least 1;
+ *       *M = the total mass, *n_mass = the number of positions that count.  One call serves all columns and probabilities with one
+ *       read-back.  Fails when no position carries mass and when the total mass would reach 2^63 (weights that were never
+ *       normalised).  Like the two calls above it only reads the population and leaves no state behind.                  */
+ABCDEZ_API int abcdez_posterior_wquantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0,
+                                           const double* slot1, const double* wns, int32_t k0, int32_t nk, const double* probs,
+                                           int32_t n_probs, double* q_out /* HOST, nk x n_probs, [k - k0][q] */, uint64_t* M,
+                                           int64_t* n_mass);
 
 /* Test hooks: evaluate the spec arithmetic on the device (fn: 0 log, 1 exp, 2 sincos2pi,
  * 3 rint, 4 floor, 5 sqrt, 6 x/y2, 7 table log, 8 table sincos2pi, 9 sqrt_pn, 10 lgamma,

@@ -904,7 +904,30 @@ ABZ_HD double abz_tree_sum_small(const double* x, int p2) { /* p2 = power of two
  * Marginal quantiles: for parameter k and probability p the type-7 quantile (Julia's default, as at smc:301) of
  * {x_ik : w_i > 0}: with n = n_pos and v the values in the total order of their IEEE bit patterns (-0.0 below +0.0),
  *   h = (n - 1) p + 1,  j = clamp(floor(h), 1, max(n - 1, 1)),  g = h - j,  q = v_j + g (v_j+1 - v_j)   (v_2 = v_1 when n = 1).
- * It is unweighted, so it is defined only where the positive weights are all equal: an indicator ABCk, or abcdemc. */
+ * It is unweighted, so it is defined only where the positive weights are all equal: an indicator ABCk, or abcdemc.
+ *
+ * WEIGHTED marginal quantiles (every ABCk; StatsBase's quantile(v, w::AbstractWeights, p) for non-frequency weights, carried out in
+ * exact integers so that no summation order exists).  This text binds the implementations.
+ *   Mass and counting.  The mass of a position is m_i = abz_weight_fix(w_i, N) -- the resampler's fixed point above,
+ *   rint(w_i N 2^b), b = abz_stratum_bits(N); with no weight array (abcdemc) every position has m_i = 2^b, i.e. w_i = 1 / N.  A position
+ *   COUNTS iff m_i >= 1 (deliberately not "w_i > 0": a weight below 2^-(b+1) / N carries no mass).  n_mass = the number of positions
+ *   that count, M = sum m_i as an exact uint64.  The call fails, and never wraps, if M would reach 2^63 (weights that were never
+ *   normalised), and if n_mass = 0.
+ *   Order.  The counting positions ordered by (order key of x_i, m_i) ascending, the order key being the IEEE total order above
+ *   (-0.0 below +0.0); ties in both components are indistinguishable.  (v_1, m_(1)) .. (v_n, m_(n)), S_k = m_(1) + .. + m_(k), S_0 = 0.
+ *   Quantile at p in [0, 1]:
+ *     t = min(floor(p (double)(M - m_(1))), M - m_(1))      one double multiplication of p by the correctly rounded conversion
+ *     H = m_(1) + t                                         an integer
+ *     n = 1, or no k has S_k > H (that is p = 1):  q = v_n
+ *     otherwise, with the smallest k that has S_k > H (always k >= 2, because S_1 = m_(1) <= H):
+ *       g = (double)(H - S_k-1) / (double)m_(k),   q = v_k-1 + g (v_k - v_k-1)      no contraction: abz_quantile_type7(v_k-1, v_k, g)
+ *   What an order-free implementation needs, for G = the positions whose value equals v_k: B = the mass of all values below v_k;
+ *   if H - B >= the smallest mass in G the crossing is not in G's first element, v_k-1 = v_k and q = v_k + g 0 (+0.0 for v_k =
+ *   -0.0, NaN for an infinite v_k, as the formula says); otherwise q = vprev + ((H - B) / m_min(G)) (v_k - vprev) with vprev the
+ *   largest counting value below v_k.  m_(1) is the smallest mass among the positions holding the smallest value.  All of these are
+ *   integer sums, minima and maxima: any evaluation order gives the same bits.
+ *   Worked: values (1, 2, 4), weights (.25, .25, .5), N = 3: p = 0, .5, 1 -> 1, 2.5, 4.  Values (2, 1, 2, 4), weights (.125, .25, .125,
+ *   .5), N = 4: p = .5 -> 2.5.  For equal weights and no ties this is type 7 up to the dropped fraction of H. */
 ABZ_HD double abz_summary_term1(double w, double x) { return w * x; }
 ABZ_HD double abz_summary_term2(double w, double xj, double mean_j, double xk, double mean_k) {
   return w * ((xj - mean_j) * (xk - mean_k));

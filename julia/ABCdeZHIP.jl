@@ -493,7 +493,9 @@ end
 # extracts as mean(r.P[r.Wns .> 0.0]), with covariance and marginal type-7 quantiles -- a few numbers per parameter instead of
 # every row.  packed = true: the abcdesmc population with its weights; packed = false: abcdemc's rows, every particle counts once.
 # cov = S / (W - Q / W) (corrected) or S / W, in plain Float64 arithmetic as every host of the library does it.
-function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, corrected::Bool=true, quantiles=Float64[])
+# wquantiles: probabilities of the WEIGHTED marginal quantiles (abcdez_spec.h, "weighted quantiles"; library version 630) -- every
+# ABCk, the Epanechnikov kernels' unequal weights included, where `quantiles` is refused; one call for all columns.
+function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, corrected::Bool=true, quantiles=Float64[], wquantiles=Float64[])
     # added with library version 620; MIN_VERSION stays where it is, so the calls are probed for
     ccall((:abcdez_version, LIB), Cint, ()) >= 620 || error("ABCdeZHIP: posterior_summary needs libabcdez_hip.so version 620 or later (rebuild the library)")
     bits = packed ? e.bits[e.bc] : C_NULL; s0 = packed ? e.slot[1] : e.slot[e.cur]; s1 = packed ? e.slot[2] : C_NULL
@@ -510,8 +512,17 @@ function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, correct
                     e.ctx, bits, e.N, s0, s1, w, k - 1, probs, length(probs), q))
         qs[:, k] = q
     end
+    wprobs = collect(Float64, wquantiles); wq = Matrix{Float64}(undef, length(wprobs), e.d)     # column-major: [q, k] = the library's [k][q]
+    M = UInt64[0]; nmass = Ref(Int64(0))
+    if !isempty(wprobs)
+        ccall((:abcdez_version, LIB), Cint, ()) >= 630 || error("ABCdeZHIP: wquantiles needs libabcdez_hip.so version 630 or later (rebuild the library)")
+        check(ccall((:abcdez_posterior_wquantiles, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{UInt64}, Ref{Int64}),
+                    e.ctx, bits, e.N, s0, s1, w, 0, e.d, wprobs, length(wprobs), wq, M, nmass))
+    end
     den = corrected ? W[] - Q[] / W[] : W[]
-    (mean = mean, cov = cov ? S ./ den : nothing, quantiles = qs, W = W[], ess = W[] * W[] / Q[], n_pos = Int(npos[]))
+    (mean = mean, cov = cov ? S ./ den : nothing, quantiles = qs, W = W[], ess = W[] * W[] / Q[], n_pos = Int(npos[]),
+     wquantiles = wq, M = isempty(wprobs) ? nothing : M[1], n_mass = isempty(wprobs) ? nothing : Int(nmass[]))
 end
 # the drivers' `summary` keyword: true, or a NamedTuple of the options above, e.g. (quantiles = [0.025, 0.975],)
 summary_of(e, summary; packed::Bool) = summary === nothing ? nothing :
