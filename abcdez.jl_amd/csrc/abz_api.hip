@@ -3,8 +3,11 @@
  * Argument checking, context life cycle and the host ends of the scalar-returning
  * calls; all device work is launched from the kernel files.
  */
+#include <float.h>
 #include <stddef.h>
 #include <string.h>
+#include <algorithm>
+#include <vector>
 
 #include "../../include/abcdez_hip.h"
 #include <chrono>
@@ -104,10 +107,10 @@ extern "C" {
 
 /* 400: Philox4x32-10 again, abz_model.mv, group abort; 401: abcdemc's better particle by rejection;
  * 500: abcdez_comm_* and abcdez_smc_sweeps_sharded (RCCL behind the ABI), timing mode 3; 600: abcdez_comm_init_host (a host-supplied
- * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles.  Hosts refuse a library older than the
+ * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms.  Hosts refuse a library older than the
  * header they were written against (abcdez.jl_amd/_lib.py, julia/ABCdeZHIP.jl check_abi): a signature that grew an argument links
  * against an old binary without a diagnostic. */
-int abcdez_version(void) { return 630; }
+int abcdez_version(void) { return 640; }
 int abcdez_rng_rounds(void) { return ABZ_PHILOX_ROUNDS; }
 
 /* sizeof / offsetof of the two structs that cross the boundary, so that a host that mirrors them by hand (the Julia
@@ -1506,6 +1509,50 @@ int abcdez_posterior_wquantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N
   for (int32_t q = 0; q < n_probs; ++q)
     ABZ_REQUIRE(probs[q] >= 0.0 && probs[q] <= 1.0, "posterior_wquantiles: p must be in [0, 1]");
   return abz_posterior_wquantiles_impl(ctx, bits, N, slot0, slot1, wns, k0, nk, probs, n_probs, q_out, M, n_mass);
+}
+
+/* Marginal and pairwise histograms over the same integer masses (csrc/abz_hist.hip); like its neighbours it only reads the
+ * population. */
+int abcdez_posterior_histograms(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                const double* wns, const int32_t* cols, int32_t n_cols, int32_t bins, const double* range,
+                                const int32_t* pairs, int32_t n_pairs, int32_t bins2, double* lo_hi, uint64_t* mass1,
+                                uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass) {
+  ABZ_REQUIRE(ctx && slot0 && lo_hi && mass1 && tallies1 && M && n_mass, "posterior_histograms: null argument");
+  ABZ_REQUIRE(!bits || slot1, "posterior_histograms: packed storage (bits) needs both row slots");
+  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_histograms: N out of range");
+  const int32_t d = (int32_t)ctx->h_model.d;
+  ABZ_REQUIRE(n_cols >= 1 && n_cols <= d, "posterior_histograms: the columns must be 1 <= n_cols <= length(prior)");
+  std::vector<char> asked((size_t)d, 0);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const int32_t k = cols ? cols[c] : c;
+    ABZ_REQUIRE(k >= 0 && k < d && (c == 0 || k > (cols ? cols[c - 1] : c - 1)),
+                "posterior_histograms: the columns must be strictly increasing in 0 .. length(prior) - 1");
+    asked[(size_t)k] = 1;
+  }
+  ABZ_REQUIRE(bins >= 1 && bins <= ABZ_HIST_MAX_BINS, "posterior_histograms: bins must be in 1 .. 4096");
+  if (range)
+    for (int32_t c = 0; c < n_cols; ++c) {
+      const double lo = range[2 * c], hi = range[2 * c + 1], w = hi - lo;
+      ABZ_REQUIRE(lo < hi && lo >= -DBL_MAX && hi <= DBL_MAX && w <= DBL_MAX,
+                  "posterior_histograms: a range must be finite with lo < hi and hi - lo finite");
+    }
+  ABZ_REQUIRE(n_pairs >= 0, "posterior_histograms: n_pairs must not be negative");
+  if (n_pairs > 0) {
+    ABZ_REQUIRE(pairs && mass2 && outside2, "posterior_histograms: pairs need the pair list, mass2 and outside2");
+    ABZ_REQUIRE(d >= 2, "posterior_histograms: pairs need at least two parameters");
+    ABZ_REQUIRE(bins2 >= 1 && bins2 <= ABZ_HIST_MAX_BINS2, "posterior_histograms: bins2 must be in 1 .. 128");
+    for (int32_t q = 0; q < n_pairs; ++q) {
+      const int32_t j = pairs[2 * q], k = pairs[2 * q + 1];
+      ABZ_REQUIRE(j >= 0 && k < d && j < k, "posterior_histograms: a pair (j, k) needs two distinct columns with j < k");
+      ABZ_REQUIRE(asked[(size_t)j] && asked[(size_t)k], "posterior_histograms: both columns of a pair must be among the requested columns");
+    }
+    std::vector<int64_t> seen((size_t)n_pairs);
+    for (int32_t q = 0; q < n_pairs; ++q) seen[(size_t)q] = (int64_t)pairs[2 * q] * d + pairs[2 * q + 1];
+    std::sort(seen.begin(), seen.end());
+    ABZ_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "posterior_histograms: a pair must not be listed twice");
+  }
+  return abz_posterior_histograms_impl(ctx, bits, N, slot0, slot1, wns, cols, n_cols, bins, range, pairs, n_pairs, bins2, lo_hi, mass1,
+                                       tallies1, mass2, outside2, M, n_mass);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

@@ -496,6 +496,33 @@ class HipOps:
             C.byref(M), C.byref(n_mass)))
         return q, M.value, n_mass.value
 
+    def posterior_histograms(self, bits, slot0, slot1, wns, N, columns=None, bins=64, range=None, pairs=(), bins2=None):
+        """(lo_hi[n_cols, 2], mass1[n_cols, bins], tallies1[n_cols, 3], mass2[n_pairs, bins2, bins2], outside2[n_pairs], M, n_mass):
+        marginal and pairwise histograms over the integer masses of the resampler, one library call (abcdez_posterior_histograms).
+        ``columns``: strictly increasing parameter indices (None: all); ``range``: n_cols x 2 or None for the automatic range;
+        ``pairs``: (j, k) parameter indices"""
+        cols = np.arange(self.spec.d, dtype=np.int32) if columns is None else np.ascontiguousarray(columns, dtype=np.int32).reshape(-1)
+        nc = int(cols.size)
+        bins, bins2 = int(bins), int(bins if bins2 is None else bins2)
+        rg = None if range is None else np.ascontiguousarray(range, dtype=np.float64).reshape(-1)
+        if rg is not None and rg.size != 2 * nc:
+            raise ValueError("posterior_histograms: range must hold (lo, hi) per requested column")
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        npairs = int(pr.shape[0])
+        lo_hi = np.empty((nc, 2), dtype=np.float64)
+        mass1 = np.zeros((nc, max(bins, 0)), dtype=np.uint64)
+        tallies1 = np.zeros((nc, 3), dtype=np.uint64)
+        b2 = max(bins2, 0) if npairs else 0
+        mass2 = np.zeros((npairs, b2, b2), dtype=np.uint64)
+        outside2 = np.zeros(npairs, dtype=np.uint64)
+        M, n_mass = C.c_uint64(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn("abcdez_posterior_histograms", 640)(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), cols.ctypes.data, nc, bins,
+            None if rg is None else rg.ctypes.data, pr.ctypes.data if npairs else None, npairs, bins2, lo_hi.ctypes.data,
+            mass1.ctypes.data, tallies1.ctypes.data, mass2.ctypes.data if npairs else None, outside2.ctypes.data if npairs else None,
+            C.byref(M), C.byref(n_mass)))
+        return lo_hi, mass1, tallies1, mass2, outside2, M.value, n_mass.value
+
     def set_stamps(self, cur, nxt):
         _lib.check(self.lib, self.lib.abcdez_ctx_set_stamps(self.ctx, _ptr(cur), _ptr(nxt)))
 
@@ -1279,7 +1306,7 @@ class PopulationEngine:
         w = self.wns
         return ((w[:, None] * th).sum(dim=0) / w.sum()).cpu().numpy()
 
-    def posterior_summary(self, cov: bool = True, corrected: bool = True, quantiles=(), wquantiles=()):
+    def posterior_summary(self, cov: bool = True, corrected: bool = True, quantiles=(), wquantiles=(), hist=None):
         """Posterior summaries of the population where it lives (include/abcdez_spec.h, "posterior summaries"): a record with
         ``mean`` (d), ``cov`` (d x d; None without ``cov``), ``quantiles`` (len(quantiles) x d marginal type-7 quantiles over the
         particles with a positive weight), ``W = sum(Wns)``, ``ess = W^2 / sum(Wns^2)`` and ``n_pos = #(Wns > 0)``; abcdemc has no
@@ -1291,7 +1318,14 @@ class PopulationEngine:
         ``wquantiles``: probabilities of the WEIGHTED marginal quantiles (include/abcdez_spec.h, "weighted quantiles"), for every
         ABC kernel -- the Epanechnikov kernels' unequal weights included, where ``quantiles`` is refused.  They come back as
         ``wquantiles`` (len(wquantiles) x d) with the total integer mass ``M`` and ``n_mass``, the number of positions that carry
-        mass; one library call and one read-back serve all columns and probabilities."""
+        mass; one library call and one read-back serve all columns and probabilities.
+
+        ``hist``: ``dict(bins=64, range=None, columns=None, pairs=None | "all" | [(j, k), ...], bins2=None)`` (or True for these
+        defaults) asks for the marginal histograms of ``columns`` and the pairwise ones of ``pairs`` (include/abcdez_spec.h,
+        "histograms") over the same integer masses: the record's ``hist`` (None when not asked for) holds ``columns``, ``lo``,
+        ``hi``, ``edges``, ``mass1`` (uint64), ``under``, ``over``, ``nan``, ``pairs``, ``bins2``, ``edges2``, ``mass2`` (uint64,
+        n_pairs x bins2 x bins2), ``outside2``, ``M``, ``n_mass`` and the host helper ``density()``.  ``range`` is (lo, hi) for all
+        or one per column; None: the smallest and largest counting value of each column.  ``bins2`` defaults to min(bins, 128)."""
         from . import summary as _summary
 
         probs = tuple(float(p) for p in quantiles)
@@ -1301,7 +1335,7 @@ class PopulationEngine:
         if not hasattr(self.ops, "posterior_moments"):
             res = self.result()
             return _summary.summary_reference(res["P"], res["Wns"] if self.packed else None, cov=cov, corrected=corrected,
-                                              quantiles=probs, wquantiles=wprobs)
+                                              quantiles=probs, wquantiles=wprobs, hist=hist)
         self._stream()
         if self.packed:
             pop = (self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns)
@@ -1316,7 +1350,13 @@ class PopulationEngine:
         if wprobs:
             q, M, n_mass = self.ops.posterior_wquantiles(*pop, self.N, wprobs)
             wq = np.ascontiguousarray(q.T)
-        return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass)
+        h = None
+        if hist is not None and hist is not False:
+            cols, bins, rng_, pairs, bins2 = _summary.hist_options(hist, self.spec.d)
+            lo_hi, mass1, tallies1, mass2, outside2, M, n_mass = self.ops.posterior_histograms(
+                *pop, self.N, columns=cols, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
+            h = _summary.make_hist(cols, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
+        return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass, h)
 
     def _to_host(self, tensors):
         """device tensors -> numpy arrays.  On the GPU: contiguous copies into PINNED host memory, all enqueued back to back on

@@ -147,9 +147,10 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     path of a file written by :func:`save_checkpoint`) continues the run.  All randomness is counter-based,
     so a resumed run reproduces the uninterrupted one bit for bit.
 
-    Posterior summaries: ``summary=True`` (or a dict of the options ``cov``, ``corrected``, ``quantiles`` of
-    :meth:`PopulationEngine.posterior_summary`) puts weighted mean, covariance, marginal quantiles, ``W``, ``ess`` and
-    ``n_pos`` of the final population into ``r.summary``, computed where the population lives.  ``download=False`` (needs
+    Posterior summaries: ``summary=True`` (or a dict of the options ``cov``, ``corrected``, ``quantiles``, ``wquantiles``,
+    ``hist`` of :meth:`PopulationEngine.posterior_summary`) puts weighted mean, covariance, marginal quantiles, ``W``, ``ess``
+    and ``n_pos`` of the final population into ``r.summary``, computed where the population lives; ``hist=dict(bins=64,
+    pairs="all", bins2=32)`` adds the marginal and pairwise histograms as ``r.summary.hist``.  ``download=False`` (needs
     ``summary``) then skips the download of the rows: ``r.P``, ``r.Wns``, ``r.C`` and ``r.blobs`` are None.
     """
     sum_opts = _summary_options(summary, download)

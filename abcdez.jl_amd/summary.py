@@ -10,6 +10,7 @@ what an engine without the device call (the CPU test engine) computes from its d
 from __future__ import annotations
 
 import math
+from builtins import range as builtins_range     # hist_reference has a `range` argument
 from types import SimpleNamespace
 
 import numpy as np
@@ -66,7 +67,7 @@ def cov_denominator(W: float, Q: float, corrected: bool) -> float:
     return W - Q / W if corrected else W
 
 
-def make_summary(mean, S, W, Q, n_pos, quantiles, probs, corrected=True, wquantiles=None, wprobs=(), M=None, n_mass=None):
+def make_summary(mean, S, W, Q, n_pos, quantiles, probs, corrected=True, wquantiles=None, wprobs=(), M=None, n_mass=None, hist=None):
     """the record ``posterior_summary`` returns, from what the library (or the restatement below) computes"""
     W, Q = float(W), float(Q)
     cov = None if S is None else np.asarray(S, dtype=np.float64) / cov_denominator(W, Q, corrected)
@@ -74,7 +75,8 @@ def make_summary(mean, S, W, Q, n_pos, quantiles, probs, corrected=True, wquanti
         wquantiles = np.empty((0, np.asarray(mean).shape[0]))
     return SimpleNamespace(mean=np.asarray(mean, dtype=np.float64), cov=cov, S=S, W=W, Q=Q, ess=W * W / Q, n_pos=int(n_pos),
                            quantiles=quantiles, probs=tuple(probs), corrected=bool(corrected), wquantiles=wquantiles,
-                           wprobs=tuple(wprobs), M=None if M is None else int(M), n_mass=None if n_mass is None else int(n_mass))
+                           wprobs=tuple(wprobs), M=None if M is None else int(M), n_mass=None if n_mass is None else int(n_mass),
+                           hist=hist)
 
 
 def stratum_bits(n: int) -> int:
@@ -150,12 +152,170 @@ def wquantiles_reference(X, w, probs):
     return out, M, len(idx)
 
 
-def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquantiles=()):
+HIST_MAX_BINS, HIST_MAX_BINS2 = 4096, 128      # ABZ_HIST_MAX_BINS, ABZ_HIST_MAX_BINS2
+HIST_OPTIONS = ("bins", "range", "columns", "pairs", "bins2")
+
+
+class Hist(SimpleNamespace):
+    """the ``hist`` field of a summary record: ``columns`` (the requested parameters), ``lo`` / ``hi`` / ``edges`` (n_cols x
+    (bins + 1), for drawing), ``mass1`` (uint64, n_cols x bins) with the tallies ``under`` / ``over`` / ``nan``, ``pairs``,
+    ``bins2``, ``edges2``, ``mass2`` (uint64, n_pairs x bins2 x bins2, [pair][b_j][b_k]), ``outside2``, ``M``, ``n_mass``"""
+
+    def density(self):
+        """mass1 / M / bin width as float64 (n_cols x bins): a convenience for drawing, not pinned bit for bit"""
+        width = (self.hi - self.lo) / float(self.bins)
+        return self.mass1.astype(np.float64) / float(self.M) / width[:, None]
+
+
+def hist_edges(lo, hi, bins):
+    """edges[c][j] = lo + j ((hi - lo) / bins), edges[c][bins] = hi"""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    e = lo[:, None] + np.arange(bins + 1, dtype=np.float64)[None, :] * ((hi - lo) / float(bins))[:, None]
+    e[:, bins] = hi
+    return e
+
+
+def make_hist(columns, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass):
+    """the ``hist`` record from what the library (or the restatement below) computes"""
+    lo_hi = np.asarray(lo_hi, dtype=np.float64).reshape(len(columns), 2)
+    lo, hi = lo_hi[:, 0].copy(), lo_hi[:, 1].copy()
+    t = np.asarray(tallies1, dtype=np.uint64).reshape(len(columns), 3)
+    has2 = len(pairs) > 0
+    return Hist(columns=tuple(int(c) for c in columns), bins=int(bins), lo=lo, hi=hi, edges=hist_edges(lo, hi, bins),
+                mass1=np.asarray(mass1, dtype=np.uint64).reshape(len(columns), bins), under=t[:, 0].copy(), over=t[:, 1].copy(),
+                nan=t[:, 2].copy(), pairs=tuple((int(j), int(k)) for j, k in pairs), bins2=int(bins2) if has2 else None,
+                edges2=hist_edges(lo, hi, bins2) if has2 else None,
+                mass2=np.asarray(mass2, dtype=np.uint64).reshape(len(pairs), bins2, bins2) if has2 else np.zeros((0, 0, 0), np.uint64),
+                outside2=np.asarray(outside2, dtype=np.uint64).reshape(len(pairs)) if has2 else np.zeros(0, np.uint64),
+                M=int(M), n_mass=int(n_mass))
+
+
+def hist_options(hist, d: int):
+    """the ``hist`` option (a dict of bins / range / columns / pairs / bins2, or True for the defaults) checked against the limits
+    of include/abcdez_spec.h ("histograms") -> (columns, bins, range (n_cols x 2) or None, pairs, bins2).  ``columns`` may come in
+    any order and are returned sorted (the order of every per-column field of the record); a per-column ``range`` is given in the
+    caller's order of ``columns`` and its rows are sorted along with them."""
+    if hist is True:
+        hist = {}
+    if not isinstance(hist, dict):
+        raise ValueError("summary: hist must be True or a dict of the options bins, range, columns, pairs, bins2")
+    bad = set(hist) - set(HIST_OPTIONS)
+    if bad:
+        raise ValueError(f"summary: unknown hist option(s) {sorted(bad)} (bins, range, columns, pairs, bins2)")
+    bins = int(hist.get("bins", 64))
+    if not 1 <= bins <= HIST_MAX_BINS:
+        raise ValueError("summary: hist bins must be in 1 .. 4096")
+    cols = hist.get("columns")
+    asked = list(range(d)) if cols is None else [int(c) for c in cols]      # the caller's order: that of a per-column range
+    cols = sorted(asked)
+    if not cols or len(set(cols)) != len(cols) or cols[0] < 0 or cols[-1] >= d:
+        raise ValueError("summary: hist columns must be distinct parameter indices in 0 .. length(prior) - 1")
+    rng_ = hist.get("range")
+    if rng_ is not None:
+        rng_ = np.array(rng_, dtype=np.float64)
+        if rng_.shape == (2,):
+            rng_ = np.tile(rng_, (len(cols), 1))
+        if rng_.shape != (len(cols), 2):
+            raise ValueError("summary: hist range must be (lo, hi) or one (lo, hi) per requested column")
+        with np.errstate(over="ignore", invalid="ignore"):
+            ok = np.isfinite(rng_).all() and (rng_[:, 0] < rng_[:, 1]).all() and np.isfinite(rng_[:, 1] - rng_[:, 0]).all()
+        if not ok:
+            raise ValueError("summary: a hist range must be finite with lo < hi and hi - lo finite")
+        rng_ = np.ascontiguousarray(rng_[[asked.index(c) for c in cols]])      # row i belongs to columns[i] as given: sorted along
+    pairs = hist.get("pairs")
+    if pairs is None:
+        pairs = []
+    elif isinstance(pairs, str):
+        if pairs != "all":
+            raise ValueError('summary: hist pairs must be None, "all" or a list of (j, k)')
+        if d < 2:
+            raise ValueError("summary: hist pairs need at least two parameters")
+        pairs = [(j, k) for a, j in enumerate(cols) for k in cols[a + 1:]]
+    else:
+        pairs = [(int(j), int(k)) for j, k in pairs]
+        if pairs and d < 2:
+            raise ValueError("summary: hist pairs need at least two parameters")
+        for j, k in pairs:
+            if not (0 <= j < k < d):
+                raise ValueError("summary: a hist pair (j, k) needs two distinct columns with j < k")
+            if j not in cols or k not in cols:
+                raise ValueError("summary: both columns of a hist pair must be among the requested columns")
+        if len(set(pairs)) != len(pairs):
+            raise ValueError("summary: a hist pair must not be listed twice")
+    bins2 = hist.get("bins2")
+    bins2 = min(bins, HIST_MAX_BINS2) if bins2 is None else int(bins2)
+    if pairs and not 1 <= bins2 <= HIST_MAX_BINS2:
+        raise ValueError("summary: hist bins2 must be in 1 .. 128")
+    return cols, bins, rng_, pairs, bins2
+
+
+def hist_bin(x, lo: float, hi: float, scale: float, bins: int):
+    """abz_hist_bin of every x: 0 .. bins - 1, or bins (under), bins + 1 (over), bins + 2 (NaN)"""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = np.floor((x - lo) * scale)                     # one subtraction, one multiplication, a floor
+        b = np.where(f >= float(bins), float(bins - 1), np.where(f >= 1.0, f, 0.0)).astype(np.int64)
+        return np.where(x != x, bins + 2, np.where(x < lo, bins, np.where(x > hi, bins + 1, b)))
+
+
+def hist_reference(X, w, bins=64, range=None, columns=None, pairs=None, bins2=None):
+    """The histograms of include/abcdez_spec.h ("posterior summaries", histograms) of the population X (N x d) with the weights w
+    (None: every position has the mass 2^b), literally: Python-integer masses, abz_hist_bin, integer sums.  Returns the record
+    of :func:`make_hist`; refuses like the library."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    N, d = X.shape
+    cols, bins, rng_, pairs, bins2 = hist_options(dict(bins=bins, range=range, columns=columns, pairs=pairs, bins2=bins2), d)
+    masses = [1 << stratum_bits(N)] * N if w is None else weight_fix(w, N)
+    idx = [i for i in builtins_range(N) if masses[i] >= 1]
+    if not idx:
+        raise ValueError("summary: no particle has a positive weight that carries mass")
+    M = sum(masses)
+    if M >= 1 << 63:
+        raise ValueError("summary: the total mass reaches 2^63 -- the weights are not normalised")
+    m = np.array([masses[i] for i in idx], dtype=np.uint64)        # every mass and every sum is below 2^63: exact in uint64
+    nc = len(cols)
+    lo_hi = np.empty((nc, 2))
+    codes1 = np.empty((nc, len(idx)), dtype=np.int64)
+    codes2 = np.empty((nc, len(idx)), dtype=np.int64)
+    for c, k in enumerate(cols):
+        x = X[idx, k]                                              # rows that do not count are never read
+        if rng_ is None:
+            keys = order_keys(x)
+            lo, hi = float(x[np.argmin(keys)]), float(x[np.argmax(keys)])
+            if lo == hi:
+                lo, hi = lo - 0.5, hi + 0.5
+            with np.errstate(over="ignore", invalid="ignore"):
+                if not (lo < hi and math.isfinite(lo) and math.isfinite(hi) and math.isfinite(hi - lo)):
+                    raise ValueError(f"summary: the automatic range of column {k} is not usable (a NaN or an infinity among the "
+                                     "counting rows, or hi - lo not finite): pass a range")
+        else:
+            lo, hi = float(rng_[c, 0]), float(rng_[c, 1])
+        lo_hi[c] = lo, hi
+        codes1[c] = hist_bin(x, lo, hi, float(bins) / (hi - lo), bins)
+        codes2[c] = hist_bin(x, lo, hi, float(bins2) / (hi - lo), bins2)
+    cells1 = np.zeros((nc, bins + 3), dtype=np.uint64)
+    for c in builtins_range(nc):
+        np.add.at(cells1[c], codes1[c], m)
+    mass2 = np.zeros((len(pairs), bins2 * bins2), dtype=np.uint64)
+    outside2 = np.zeros(len(pairs), dtype=np.uint64)
+    where = {k: c for c, k in enumerate(cols)}
+    for q, (j, k) in enumerate(pairs):
+        bj, bk = codes2[where[j]], codes2[where[k]]
+        inside = (bj < bins2) & (bk < bins2)
+        np.add.at(mass2[q], bj[inside] * bins2 + bk[inside], m[inside])
+        outside2[q] = m[~inside].sum(dtype=np.uint64)
+    return make_hist(cols, bins, lo_hi, cells1[:, :bins], cells1[:, bins:], pairs, bins2, mass2, outside2, M, len(idx))
+
+
+def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquantiles=(), hist=None):
     """numpy restatement of the summary arithmetic.  ``P``: the push_p-cast population, shape (N,) or (N, d) (``r.P``);
     ``Wns``: the weights (``r.Wns``), or None for unit weights (abcdemc).  Returns the record of :func:`make_summary`:
     ``mean`` (d), ``cov`` (d x d, or None), ``S`` (the unnormalised second central moments), ``quantiles``
     (len(quantiles) x d), ``W``, ``Q``, ``ess = W^2 / Q``, ``n_pos``, and for ``wquantiles`` the weighted quantiles ``wquantiles``
-    (len(wquantiles) x d) with the total integer mass ``M`` and ``n_mass`` (both None when none are asked for)."""
+    (len(wquantiles) x d) with the total integer mass ``M`` and ``n_mass`` (both None when none are asked for), and for ``hist``
+    (the options of :func:`hist_reference`) the record ``hist`` of the marginal and pairwise histograms (None otherwise)."""
     X = np.asarray(P, dtype=np.float64)
     if X.ndim == 1:
         X = X[:, None]
@@ -200,19 +360,24 @@ def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquan
     wq = M = n_mass = None
     if wprobs:
         wq, M, n_mass = wquantiles_reference(X, None if Wns is None else w, wprobs)
-    return make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass)
+    h = None
+    if hist is not None and hist is not False:
+        hist_options(hist, d)
+        h = hist_reference(X, None if Wns is None else w, **({} if hist is True else hist))
+        M, n_mass = h.M, h.n_mass
+    return make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass, h)
 
 
 def summary_options(summary) -> dict:
-    """the ``summary=`` keyword of the drivers: True, or a dict of cov / corrected / quantiles / wquantiles"""
+    """the ``summary=`` keyword of the drivers: True, or a dict of cov / corrected / quantiles / wquantiles / hist"""
     if summary is True:
         return {}
     if isinstance(summary, dict):
-        bad = set(summary) - {"cov", "corrected", "quantiles", "wquantiles"}
+        bad = set(summary) - {"cov", "corrected", "quantiles", "wquantiles", "hist"}
         if bad:
-            raise ValueError(f"summary: unknown option(s) {sorted(bad)} (cov, corrected, quantiles, wquantiles)")
+            raise ValueError(f"summary: unknown option(s) {sorted(bad)} (cov, corrected, quantiles, wquantiles, hist)")
         return dict(summary)
-    raise ValueError("summary must be None, True or a dict of the options cov, corrected, quantiles, wquantiles")
+    raise ValueError("summary must be None, True or a dict of the options cov, corrected, quantiles, wquantiles, hist")
 
 
 def engine_summary(eng, **opts):

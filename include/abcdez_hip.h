@@ -452,6 +452,23 @@ ABCDEZ_API int abcdez_posterior_wquantiles(abcdez_ctx* ctx, const uint32_t* bits
                                            const double* slot1, const double* wns, int32_t k0, int32_t nk, const double* probs,
                                            int32_t n_probs, double* q_out /* HOST, nk x n_probs, [k - k0][q] */, uint64_t* M,
                                            int64_t* n_mass);
+/*     posterior_histograms (library version 640): marginal and pairwise histograms of abcdez_spec.h ("posterior summaries",
+ *       histograms) over the same integer masses, for every ABC kernel and for wns == NULL (mass 2^b each).  cols[n_cols] (HOST,
+ *       strictly increasing; NULL: the parameters 0 .. n_cols - 1) are the requested columns, `bins` (1 .. 4096) their 1-D bins;
+ *       range (HOST, n_cols x 2: lo, hi per requested column) or NULL for the automatic range, the smallest and largest value
+ *       over the counting positions (a constant column: +- 0.5).  pairs[n_pairs][2] (HOST, parameter indices j < k, both among
+ *       the requested columns, each pair once; n_pairs may be 0, mass2 / outside2 are then not touched) with bins2 (1 .. 128) bins per axis over
+ *       the same ranges.  Outputs, all HOST: lo_hi[n_cols][2] the ranges used, mass1[n_cols][bins], tallies1[n_cols][3] =
+ *       (under, over, NaN), mass2[n_pairs][bins2][bins2] indexed [pair][b_j][b_k], outside2[n_pairs], *M the total mass, *n_mass
+ *       the number of positions that count; per column sum(mass1) + under + over + NaN == M, per pair sum(mass2) + outside2 == M.
+ *       One call serves all columns and pairs with one synchronisation.  Fails when no position carries mass, when the total
+ *       mass would reach 2^63, and when an automatic range is not finite (the message names the column: pass a range).  Like the
+ *       calls above it only reads the population and leaves no state behind.                                             */
+ABCDEZ_API int abcdez_posterior_histograms(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0,
+                                           const double* slot1, const double* wns, const int32_t* cols, int32_t n_cols,
+                                           int32_t bins, const double* range, const int32_t* pairs, int32_t n_pairs,
+                                           int32_t bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1, uint64_t* mass2,
+                                           uint64_t* outside2, uint64_t* M, int64_t* n_mass);
 
 /* Test hooks: evaluate the spec arithmetic on the device (fn: 0 log, 1 exp, 2 sincos2pi,
  * 3 rint, 4 floor, 5 sqrt, 6 x/y2, 7 table log, 8 table sincos2pi, 9 sqrt_pn, 10 lgamma,

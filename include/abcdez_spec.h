@@ -927,7 +927,44 @@ ABZ_HD double abz_tree_sum_small(const double* x, int p2) { /* p2 = power of two
  *   largest counting value below v_k.  m_(1) is the smallest mass among the positions holding the smallest value.  All of these are
  *   integer sums, minima and maxima: any evaluation order gives the same bits.
  *   Worked: values (1, 2, 4), weights (.25, .25, .5), N = 3: p = 0, .5, 1 -> 1, 2.5, 4.  Values (2, 1, 2, 4), weights (.125, .25, .125,
- *   .5), N = 4: p = .5 -> 2.5.  For equal weights and no ties this is type 7 up to the dropped fraction of H. */
+ *   .5), N = 4: p = .5 -> 2.5.  For equal weights and no ties this is type 7 up to the dropped fraction of H.
+ *
+ * HISTOGRAMS (marginal and pairwise, what examples/minimal_example.jl:89-122 of the reference draws from r.P[r.Wns .> 0]), in the same
+ * exact integers.  This text binds the implementations.
+ *   Mass and counting are those of the weighted quantiles: m_i = abz_weight_fix(w_i, N), or 2^b each with no weight array; a position
+ *   counts iff m_i >= 1; M = sum m_i, refused when it would reach 2^63, and when n_mass = 0; the row of a position that does not count
+ *   is never read for its value.  The value is x = push_p of the current row's column, as in the other summaries.
+ *   Range of a column: either given, (lo, hi) finite with lo < hi and hi - lo finite; or automatic: lo and hi are the smallest and the
+ *   largest value over the counting positions in the order-key order above (an integer minimum / maximum of order keys: order-free;
+ *   -0.0 is below +0.0).  An automatic range with lo == hi (as doubles, so also (-0.0, +0.0)) becomes (lo - 0.5, hi + 0.5).  An
+ *   automatic lo or hi that is not finite (a NaN or an infinity in a counting row), or whose hi - lo is not finite, or that still
+ *   lacks lo < hi (a constant of magnitude 2^53 or more, which 0.5 cannot widen), is an error that names the column and says to
+ *   pass a range.
+ *   Bin of x for `bins` bins: scale = (double)bins / (hi - lo), one IEEE division;
+ *     x is NaN -> tally `nan`;  x < lo -> tally `under`;  x > hi -> tally `over`;
+ *     otherwise b = min((int64)floor((x - lo) * scale), bins - 1): one subtraction, one multiplication, a floor, no contraction
+ *   (abz_hist_bin).  Membership is DEFINED by this rule -- x == hi is in the last bin, -0.0 with lo = +0.0 in bin 0.  The edges
+ *   edges[j] = lo + j ((hi - lo) / bins), edges[bins] = hi are for drawing only.
+ *   1-D, for every requested column k: mass1[k][b] += m_i (uint64) and the three tallies under[k], over[k], nan[k], so that
+ *   sum(mass1[k]) + under[k] + over[k] + nan[k] == M for every column.
+ *   2-D, for every requested pair (j, k), j < k, with bins2 bins per axis over the SAME (lo, hi) of the two columns (scale2 =
+ *   (double)bins2 / (hi - lo)): mass2[pair][b_j][b_k] += m_i iff both values are in range, else outside2[pair] += m_i; so
+ *   sum(mass2[pair]) + outside2[pair] == M.
+ *   Limits: 1 <= bins <= 4096, 1 <= bins2 <= 128; pairs need d >= 2, two distinct requested columns and j < k; a pair is listed
+ *   once.
+ *   Sums of integers only: any order of accumulation (atomics included) gives the same bits. */
+#define ABZ_HIST_MAX_BINS 4096
+#define ABZ_HIST_MAX_BINS2 128
+/* the bin of x: 0 .. bins - 1, or bins (under), bins + 1 (over), bins + 2 (NaN) */
+ABZ_HD int32_t abz_hist_bin(double x, double lo, double hi, double scale, int32_t bins) {
+  if (x != x) return bins + 2;
+  if (x < lo) return bins;
+  if (x > hi) return bins + 1;
+  const double f = abz_floor((x - lo) * scale);
+  if (!(f >= 1.0)) return 0;                       /* also -0.0 (x = -0.0, lo = +0.0) */
+  return f >= (double)bins ? bins - 1 : (int32_t)f;
+}
+ABZ_HD double abz_hist_scale(double lo, double hi, int32_t bins) { return (double)bins / (hi - lo); }
 ABZ_HD double abz_summary_term1(double w, double x) { return w * x; }
 ABZ_HD double abz_summary_term2(double w, double xj, double mean_j, double xk, double mean_k) {
   return w * ((xj - mean_j) * (xk - mean_k));

@@ -495,7 +495,11 @@ end
 # cov = S / (W - Q / W) (corrected) or S / W, in plain Float64 arithmetic as every host of the library does it.
 # wquantiles: probabilities of the WEIGHTED marginal quantiles (abcdez_spec.h, "weighted quantiles"; library version 630) -- every
 # ABCk, the Epanechnikov kernels' unequal weights included, where `quantiles` is refused; one call for all columns.
-function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, corrected::Bool=true, quantiles=Float64[], wquantiles=Float64[])
+# hist: nothing, or a NamedTuple of bins (64), range (nothing: automatic; (lo, hi) for all columns, or a d x 2 matrix), pairs
+# (nothing, :all or a vector of 0-based (j, k), j < k) and bins2 (min(bins, 128)): marginal and pairwise histograms over the same
+# integer masses (abcdez_spec.h, "histograms"; library version 640), all columns and pairs in one call.
+function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, corrected::Bool=true, quantiles=Float64[], wquantiles=Float64[],
+                           hist=nothing)
     # added with library version 620; MIN_VERSION stays where it is, so the calls are probed for
     ccall((:abcdez_version, LIB), Cint, ()) >= 620 || error("ABCdeZHIP: posterior_summary needs libabcdez_hip.so version 620 or later (rebuild the library)")
     bits = packed ? e.bits[e.bc] : C_NULL; s0 = packed ? e.slot[1] : e.slot[e.cur]; s1 = packed ? e.slot[2] : C_NULL
@@ -520,9 +524,29 @@ function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, correct
                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{UInt64}, Ref{Int64}),
                     e.ctx, bits, e.N, s0, s1, w, 0, e.d, wprobs, length(wprobs), wq, M, nmass))
     end
+    h = nothing
+    if hist !== nothing
+        ccall((:abcdez_version, LIB), Cint, ()) >= 640 || error("ABCdeZHIP: hist needs libabcdez_hip.so version 640 or later (rebuild the library)")
+        bins = Int(get(hist, :bins, 64)); bins2 = Int(something(get(hist, :bins2, nothing), min(bins, 128)))
+        pr = get(hist, :pairs, nothing)
+        pl = pr === nothing ? Tuple{Int,Int}[] : pr === :all ? [(j, k) for j in 0:e.d-1 for k in j+1:e.d-1] : collect(pr)
+        pairs = Int32[x for p in pl for x in p]; np = length(pl)                      # [j0, k0, j1, k1, ...]: the library's pairs[q][2]
+        rg = get(hist, :range, nothing)
+        range = rg === nothing ? C_NULL : rg isa Tuple ? repeat(Float64[rg[1], rg[2]], e.d) : collect(Float64, permutedims(rg))
+        lohi = Matrix{Float64}(undef, 2, e.d); mass1 = Matrix{UInt64}(undef, bins, e.d); tallies = Matrix{UInt64}(undef, 3, e.d)
+        mass2 = Array{UInt64}(undef, bins2, bins2, np); outside2 = Vector{UInt64}(undef, np)   # column-major: [b_k, b_j, pair]
+        check(ccall((:abcdez_posterior_histograms, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Int32, Int32,
+                     Ptr{Float64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ref{Int64}),
+                    e.ctx, bits, e.N, s0, s1, w, C_NULL, e.d, bins, range, np > 0 ? pairs : C_NULL, np, bins2,
+                    lohi, mass1, tallies, np > 0 ? mass2 : C_NULL, np > 0 ? outside2 : C_NULL, M, nmass))
+        h = (lo = lohi[1, :], hi = lohi[2, :], bins = bins, mass1 = mass1, under = tallies[1, :], over = tallies[2, :], nan = tallies[3, :],
+             pairs = pl, bins2 = bins2, mass2 = mass2, outside2 = outside2, M = M[1], n_mass = Int(nmass[]))
+    end
     den = corrected ? W[] - Q[] / W[] : W[]
     (mean = mean, cov = cov ? S ./ den : nothing, quantiles = qs, W = W[], ess = W[] * W[] / Q[], n_pos = Int(npos[]),
-     wquantiles = wq, M = isempty(wprobs) ? nothing : M[1], n_mass = isempty(wprobs) ? nothing : Int(nmass[]))
+     wquantiles = wq, M = (isempty(wprobs) && hist === nothing) ? nothing : M[1],
+     n_mass = (isempty(wprobs) && hist === nothing) ? nothing : Int(nmass[]), hist = h)
 end
 # the drivers' `summary` keyword: true, or a NamedTuple of the options above, e.g. (quantiles = [0.025, 0.975],)
 summary_of(e, summary; packed::Bool) = summary === nothing ? nothing :
