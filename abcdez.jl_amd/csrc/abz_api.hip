@@ -107,10 +107,10 @@ extern "C" {
 
 /* 400: Philox4x32-10 again, abz_model.mv, group abort; 401: abcdemc's better particle by rejection;
  * 500: abcdez_comm_* and abcdez_smc_sweeps_sharded (RCCL behind the ABI), timing mode 3; 600: abcdez_comm_init_host (a host-supplied
- * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms.  Hosts refuse a library older than the
+ * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms; 650: abcdez_posterior_sample.  Hosts refuse a library older than the
  * header they were written against (abcdez.jl_amd/_lib.py, julia/ABCdeZHIP.jl check_abi): a signature that grew an argument links
  * against an old binary without a diagnostic. */
-int abcdez_version(void) { return 640; }
+int abcdez_version(void) { return 650; }
 int abcdez_rng_rounds(void) { return ABZ_PHILOX_ROUNDS; }
 
 /* sizeof / offsetof of the two structs that cross the boundary, so that a host that mirrors them by hand (the Julia
@@ -1553,6 +1553,22 @@ int abcdez_posterior_histograms(abcdez_ctx* ctx, const uint32_t* bits, int64_t N
   }
   return abz_posterior_histograms_impl(ctx, bits, N, slot0, slot1, wns, cols, n_cols, bins, range, pairs, n_pairs, bins2, lo_hi, mass1,
                                        tallies1, mass2, outside2, M, n_mass);
+}
+
+/* n equally weighted draws from the population and the gather of their rows, distances and stamps (csrc/abz_sample.hip); like its
+ * neighbours it only reads the population, and its scratch is the summaries' buffer: a select armed ahead survives it. */
+int abcdez_posterior_sample(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                            const double* wns, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
+                            uint32_t* idx_out, double* P_out, double* theta_out, double* delta_out, uint64_t* stamp_out,
+                            uint64_t* M, int64_t* n_mass) {
+  ABZ_REQUIRE(ctx && slot0 && idx_out && P_out && M && n_mass, "posterior_sample: null argument");
+  ABZ_REQUIRE(!bits || slot1, "posterior_sample: packed storage (bits) needs both row slots");
+  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_sample: N out of range");
+  ABZ_REQUIRE(n >= 1 && n <= ABZ_SAMPLE_MAX_N, "posterior_sample: n must be in 1 .. 2^31 - 1");
+  ABZ_REQUIRE((delta != nullptr) == (delta_out != nullptr), "posterior_sample: delta_out is given iff delta is");
+  ABZ_REQUIRE((stamp != nullptr) == (stamp_out != nullptr), "posterior_sample: stamp_out is given iff stamp is");
+  return abz_posterior_sample_impl(ctx, bits, N, slot0, slot1, wns, n, draw, delta, stamp, idx_out, P_out, theta_out, delta_out,
+                                   stamp_out, M, n_mass);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

@@ -694,7 +694,7 @@ int abz_ind_reweight_partition(abcdez_ctx* ctx, const double* delta_all, uint8_t
 
 /* ================================================================ stratified resampling (smc:15-56)
  * integer weights (abz_weight_fix) -> inclusive scan in u64 -> per-stratum search. */
-#define ABZ_SCAN_TILE 2048 /* 256 threads x 8 consecutive elements */
+/* ABZ_SCAN_TILE (abz_ctx.h): 256 threads x 8 consecutive elements */
 
 __device__ inline void wfix_load8(const double* __restrict__ wns, uint32_t base, uint32_t N, double (&w)[8]) {
   if (base + 8u <= N) {                  /* base is a multiple of 8: 64-byte aligned */
@@ -830,6 +830,17 @@ __global__ __launch_bounds__(ABZ_BLOCK) void stratified_search_kernel(const unsi
   inds[s] = (lo >= N || lo > lp) ? lp : lo;
 }
 
+/* the scan alone, on the caller's buffers (the resampler below; the posterior sample of abz_sample.hip): tile[nt] receives the
+ * exclusive sums of the tiles, cum[n] the inclusive sums of the masses, *last_pos 1 + the last position with mass; tile_lp[nt] is
+ * scratch.  nt = ceil(n / ABZ_SCAN_TILE).  Three launches on the context's stream, nothing else is touched. */
+void abz_wfix_scan_enqueue(abcdez_ctx* ctx, const double* wns, uint32_t n, unsigned long long* tile, uint32_t* tile_lp,
+                           unsigned long long* last_pos, unsigned long long* cum) {
+  const uint32_t nt = (n + ABZ_SCAN_TILE - 1) / ABZ_SCAN_TILE;
+  hipLaunchKernelGGL(wfix_tile_sum_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, ctx->stream, wns, n, tile, tile_lp);
+  hipLaunchKernelGGL(scan_u64_kernel, dim3(1), dim3(1024), 0, ctx->stream, tile, nt, (const uint32_t*)tile_lp, last_pos);
+  hipLaunchKernelGGL(wfix_scan_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, ctx->stream, wns, n, (const unsigned long long*)tile, cum);
+}
+
 int abz_stratified_impl(abcdez_ctx* ctx, const double* wns, int64_t N, uint32_t draw, uint32_t* inds) {
   const uint32_t n = (uint32_t)N;
   const uint32_t nt = (n + ABZ_SCAN_TILE - 1) / ABZ_SCAN_TILE;
@@ -840,10 +851,7 @@ int abz_stratified_impl(abcdez_ctx* ctx, const double* wns, int64_t N, uint32_t 
   unsigned long long* tile = (unsigned long long*)ctx->ws;
   unsigned long long* cum = (unsigned long long*)((char*)ctx->ws + tb);
   uint32_t* tile_lp = (uint32_t*)((char*)ctx->ws + tb + abz_align((size_t)n * 8));
-  hipLaunchKernelGGL(wfix_tile_sum_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, ctx->stream, wns, n, tile, tile_lp);
-  hipLaunchKernelGGL(scan_u64_kernel, dim3(1), dim3(1024), 0, ctx->stream, tile, nt, (const uint32_t*)tile_lp,
-                     ctx->d_scal + ABZ_S_LASTPOS);
-  hipLaunchKernelGGL(wfix_scan_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, ctx->stream, wns, n, tile, cum);
+  abz_wfix_scan_enqueue(ctx, wns, n, tile, tile_lp, ctx->d_scal + ABZ_S_LASTPOS, cum);
   hipLaunchKernelGGL(stratified_search_kernel, dim3((n + ABZ_BLOCK - 1) / ABZ_BLOCK), dim3(ABZ_BLOCK), 0, ctx->stream,
                      cum, n, ctx->h_model.seed, draw, ctx->d_scal + ABZ_S_LASTPOS, inds);
   ABZ_HIP_CHECK(hipGetLastError());

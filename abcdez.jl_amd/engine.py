@@ -523,6 +523,25 @@ class HipOps:
             C.byref(M), C.byref(n_mass)))
         return lo_hi, mass1, tallies1, mass2, outside2, M.value, n_mass.value
 
+    def posterior_sample(self, bits, slot0, slot1, wns, N, n, draw=0, delta=None, stamp=None, want_theta=False):
+        """(index[n] int32, P[n, d], theta[n, ld] or None, delta[n] or None, stamp[n] or None, M, n_mass): n equally weighted draws
+        from the population and the gather of their rows, all DEVICE tensors; one library call, one synchronisation
+        (abcdez_posterior_sample, include/abcdez_spec.h "POSTERIOR SAMPLE")"""
+        n = int(n)
+        if not 1 <= n <= (1 << 31) - 1:
+            raise ValueError("posterior_sample: n must be in 1 .. 2^31 - 1")
+        fn = self._summary_fn("abcdez_posterior_sample", 650)
+        dev = self.device
+        idx = torch.empty(n, dtype=torch.int32, device=dev)
+        P = torch.empty((n, self.spec.d), dtype=torch.float64, device=dev)
+        theta = torch.empty((n, self.spec.ld), dtype=torch.float64, device=dev) if want_theta else None
+        dl = torch.empty(n, dtype=torch.float64, device=dev) if delta is not None else None
+        st = torch.empty(n, dtype=torch.int64, device=dev) if stamp is not None else None
+        M, n_mass = C.c_uint64(), C.c_int64()
+        _lib.check(self.lib, fn(self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), n, int(draw) & 0xFFFFFFFF, _ptr(delta),
+                                _ptr(stamp), _ptr(idx), _ptr(P), _ptr(theta), _ptr(dl), _ptr(st), C.byref(M), C.byref(n_mass)))
+        return idx, P, theta, dl, st, M.value, n_mass.value
+
     def set_stamps(self, cur, nxt):
         _lib.check(self.lib, self.lib.abcdez_ctx_set_stamps(self.ctx, _ptr(cur), _ptr(nxt)))
 
@@ -1357,6 +1376,55 @@ class PopulationEngine:
                 *pop, self.N, columns=cols, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
             h = _summary.make_hist(cols, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
         return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass, h)
+
+    def posterior_sample(self, n: int, draw: int = 0, blobs=None):
+        """``n`` equally weighted draws from the weighted population (include/abcdez_spec.h, "POSTERIOR SAMPLE"): what the
+        reference's users build by hand as ``r.P[weightinds(r.Wns)]`` (test/runtests.jl:13-19), drawn and gathered where the
+        population lives, for any n (not only N).  A record with ``P`` (n x d, or (n,) for a univariate prior, exactly
+        ``result()["P"][index]``), ``index`` (int64, the positions drawn, NON-DECREASING: shuffle for an exchangeable order), ``C``
+        (their distances), ``blobs`` (the simulated data behind them, when the engine carries stamps and ``blobs`` is not False;
+        None otherwise), ``M``, ``n_mass``, ``n`` and ``draw``.  ``draw`` selects an independent set of points (the epoch of the RNG
+        purpose ABZ_RNG_SAMPLE); no stream of the run is touched, so a run continued afterwards is bit-identical.  Only the n-row
+        outputs travel to the host, and with blobs the simulator is re-run for the n gathered rows only.  Engines without the
+        device call get :func:`abcdez_amd.summary.sample_reference` on their downloaded result."""
+        from . import summary as _summary
+
+        opts = _summary.sample_options(dict(n=n, draw=draw, blobs=blobs))
+        n, draw = opts["n"], opts["draw"]
+        if blobs and not self.blob_on:
+            raise ValueError("sample: blobs=True needs a simulator that returns blobs")
+        want_blobs = self.blob_on and blobs is not False
+        squeeze = self.spec.d == 1 and not hasattr(self.spec.prior, "p")      # the rule of result()
+        if not hasattr(self.ops, "posterior_sample"):
+            res = self.result()
+            index, M, n_mass = _summary.sample_reference(res["P"], res["Wns"] if self.packed else None, n, self.spec.seed, draw,
+                                                         rounds=self.ops.stream_version()[1])
+            return _summary.make_sample(res["P"][index], index, res["C"][index], res["blobs"][index] if want_blobs else None, M,
+                                        n_mass, n, draw)
+        self._stream()
+        self._sync_delta()
+        if self.packed:
+            pop = (self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns)
+        else:
+            pop = (None, self.buf[self.cur][0], None, None)
+        idx, P, th, dl, st, M, n_mass = self.ops.posterior_sample(
+            *pop, self.N, n, draw, delta=self.buf[self.cur][2], stamp=self.stamp[self.cur] if want_blobs else None, want_theta=want_blobs)
+        send = [idx, P, dl]
+        if want_blobs:
+            # the simulated data behind the n gathered distances, rebuilt from their stamps; as in result() the re-run's distance
+            # must be the gathered one, bit for bit
+            out = torch.zeros((n, self.ops.blob_width()), dtype=torch.float64, device=self.device)
+            redo = torch.empty_like(dl)
+            self.ops.blob_eval(th, st, out, redo)
+            if not torch.equal(redo.view(torch.int64), dl.view(torch.int64)):
+                raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
+            send.append(out[:, :self.spec.n_blob])
+        got = self._to_host(send)
+        Ph = got[1][:, 0] if squeeze else got[1]
+        bl = None
+        if want_blobs:
+            bl = got[3][:, 0] if got[3].shape[1] == 1 else got[3]
+        return _summary.make_sample(Ph, got[0].astype(np.int64), got[2], bl, M, n_mass, n, draw)
 
     def _to_host(self, tensors):
         """device tensors -> numpy arrays.  On the GPU: contiguous copies into PINNED host memory, all enqueued back to back on

@@ -102,14 +102,24 @@ def _check(cond: bool, msg: str) -> None:
         raise ValueError(msg)  # the reference raises ErrorException via error(...)
 
 
-def _summary_options(summary, download):
-    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None"""
+def _summary_options(summary, download, sample=None):
+    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None (``sample``: the drivers' keyword
+    of that name -- with it the result is not empty either)"""
     if summary is None or summary is False:
-        _check(bool(download), "download=False needs summary: the result would be empty")
+        _check(bool(download) or sample is not None, "download=False needs summary: the result would be empty")
         return None
     from .summary import summary_options
 
     return summary_options(summary)
+
+
+def _sample_options(sample):
+    """the drivers' ``sample`` keyword (an integer n, or a dict of n / draw / blobs) -> keywords of posterior_sample, or None"""
+    if sample is None:
+        return None
+    from .summary import sample_options
+
+    return sample_options(sample)
 
 
 def _make_engine(spec: ModelSpec, nparticles: int, engine, process_group, storage: str = "packed"):
@@ -131,7 +141,8 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
              nsims_max: int = 10 ** 7, Kmcmc: int = 3, Kmcmc_min: float = 1.0,
              ABCk=IndicatorStrict0toϵ, facc_stop: float = 0.0, facc_min: float = 0.0, facc_tune: float = 0.975,
              verbose: bool = True, verboseout: bool = True, rng: int = 1, parallel: bool = False,
-             engine=None, process_group=None, max_iters: int = 1_000_000, resume=None, summary=None, download: bool = True):
+             engine=None, process_group=None, max_iters: int = 1_000_000, resume=None, summary=None, download: bool = True,
+             sample=None):
     """Run ABC with differential-evolution moves in an SMC setup (src/abcdez_smc.jl:215).
 
     Same positional arguments, keywords and defaults as the reference, except:
@@ -151,9 +162,14 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     ``hist`` of :meth:`PopulationEngine.posterior_summary`) puts weighted mean, covariance, marginal quantiles, ``W``, ``ess``
     and ``n_pos`` of the final population into ``r.summary``, computed where the population lives; ``hist=dict(bins=64,
     pairs="all", bins2=32)`` adds the marginal and pairwise histograms as ``r.summary.hist``.  ``download=False`` (needs
-    ``summary``) then skips the download of the rows: ``r.P``, ``r.Wns``, ``r.C`` and ``r.blobs`` are None.
+    ``summary`` or ``sample``) then skips the download of the rows: ``r.P``, ``r.Wns``, ``r.C`` and ``r.blobs`` are None.
+
+    Posterior sample: ``sample=n`` (or ``dict(n=, draw=0, blobs=None)``) puts n equally weighted draws from the final weighted
+    population into ``r.sample`` (:meth:`PopulationEngine.posterior_sample`: ``P``, ``index``, ``C``, ``blobs``, ``M``, ``n_mass``),
+    drawn and gathered where the population lives -- ``r.sample.P`` is ``r.P[r.sample.index]`` without the download.
     """
-    sum_opts = _summary_options(summary, download)
+    smp_opts = _sample_options(sample)
+    sum_opts = _summary_options(summary, download, sample)
     # ---- initialisation / validation: src/abcdez_smc.jl:223-235
     _check(0.0 <= α < 1.0, "α must be in 0 <= α < 1")
     _check(0.0 <= δess <= 1.0, "δess must be in 0 <= δess <= 1")
@@ -274,6 +290,10 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
         from .summary import engine_summary
 
         out.summary = engine_summary(eng, **sum_opts)
+    if smp_opts is not None:
+        from .summary import engine_sample
+
+        out.sample = engine_sample(eng, **smp_opts)
     out.eps = ϵ
     out.iters, out.nsims, out.updates = iters, nsims, updates
     out.engine = eng

@@ -368,6 +368,129 @@ def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquan
     return make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass, h)
 
 
+# ------------------------------------------------------------------ posterior sample (include/abcdez_spec.h, "POSTERIOR SAMPLE")
+RNG_SAMPLE = 10                 # ABZ_RNG_SAMPLE
+SAMPLE_MAX_N = (1 << 31) - 1    # ABZ_SAMPLE_MAX_N
+SAMPLE_OPTIONS = ("n", "draw", "blobs")
+_MASK32 = 0xFFFFFFFF
+
+
+def philox4x32(ctr, key, rounds: int = 10):
+    """Philox4x32-R (Salmon et al., SC'11) of the counter (c0, c1, c2, c3) under the key (k0, k1) in Python integers:
+    abz_philox4x32 of include/abcdez_spec.h"""
+    c0, c1, c2, c3 = (int(v) & _MASK32 for v in ctr)
+    k0, k1 = (int(v) & _MASK32 for v in key)
+    for _ in range(rounds):
+        p0 = 0xD2511F53 * c0
+        p1 = 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _MASK32, (p0 >> 32) ^ c3 ^ k1, p0 & _MASK32
+        k0, k1 = (k0 + 0x9E3779B9) & _MASK32, (k1 + 0xBB67AE85) & _MASK32
+    return [c0, c1, c2, c3]
+
+
+def abz_rng(seed: int, idx: int, epoch: int, sub: int, purpose: int, rounds: int = 10):
+    """abz_rng: the two 64-bit words of the Philox block addressed by (idx, epoch, sub, purpose) under the 64-bit seed"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    r = philox4x32((idx, epoch, sub, purpose), (seed & _MASK32, seed >> 32), rounds)
+    return (r[1] << 32) | r[0], (r[3] << 32) | r[2]
+
+
+def sample_masses(Wns, N: int):
+    """the integer masses of the N positions (Python integers): abz_weight_fix of the weights, or 2^b each without weights"""
+    if Wns is None:
+        return [1 << stratum_bits(N)] * N
+    w = np.asarray(Wns, dtype=np.float64)
+    if w.shape != (N,):
+        raise ValueError("sample: one weight per particle expected")
+    return weight_fix(w, N)
+
+
+def sample_reference(P, Wns, n, seed, draw: int = 0, rounds: int = 10):
+    """The posterior sample of include/abcdez_spec.h ("posterior summaries", POSTERIOR SAMPLE), literally and in Python integers:
+    ``(index, M, n_mass)`` with ``index`` (int64, n) the positions drawn for the strata 0 .. n - 1 -- ``P[index]`` is the sample.
+    ``P``: the population (only its length is used; an int N is accepted), ``Wns``: the weights or None (abcdemc: unit masses),
+    ``seed``: the run's 64-bit seed (``rng=``), ``rounds``: the Philox rounds of the stream (``abcdez_rng_rounds()``).  Refuses like
+    the library."""
+    import bisect
+
+    N = int(P) if isinstance(P, (int, np.integer)) else int(np.asarray(P).shape[0])
+    n = int(n)
+    if N < 1:
+        raise ValueError("sample: the population is empty")
+    if not 1 <= n <= SAMPLE_MAX_N:
+        raise ValueError("sample: n must be in 1 .. 2^31 - 1")
+    masses = sample_masses(Wns, N)
+    n_mass = sum(1 for m in masses if m >= 1)
+    if n_mass < 1:
+        raise ValueError("sample: no particle has a positive weight that carries mass")
+    M = sum(masses)
+    if M >= 1 << 63:
+        raise ValueError("sample: the total mass reaches 2^63 -- the weights are not normalised")
+    if n > M:
+        raise ValueError("sample: n exceeds the total mass M")
+    q, r = divmod(M, n)
+    index = np.empty(n, dtype=np.int64)
+    if Wns is None:
+        b = stratum_bits(N)
+        cum = None
+    else:
+        cum, c = [], 0
+        for m in masses:
+            c += m
+            cum.append(c)                                  # C_i, inclusive
+    draw = int(draw) & _MASK32
+    for s in range(n):
+        a = s * q + min(s, r)
+        h = q + (1 if s < r else 0)
+        u = abz_rng(seed, s, draw, 0, RNG_SAMPLE, rounds)[0]
+        R = a + ((u * h) >> 64)
+        index[s] = (R >> b) if cum is None else bisect.bisect_right(cum, R)      # the smallest i with C_i > R
+    return index, M, n_mass
+
+
+def sample_options(sample) -> dict:
+    """the ``sample=`` keyword of the drivers: an integer n, or a dict of n / draw / blobs -> the keywords of posterior_sample"""
+    if isinstance(sample, (bool, float)) or sample is None:
+        raise ValueError("sample must be None, an integer n or a dict of the options n, draw, blobs")
+    if isinstance(sample, (int, np.integer)):
+        sample = {"n": int(sample)}
+    if not isinstance(sample, dict):
+        raise ValueError("sample must be None, an integer n or a dict of the options n, draw, blobs")
+    bad = set(sample) - set(SAMPLE_OPTIONS)
+    if bad:
+        raise ValueError(f"sample: unknown option(s) {sorted(bad)} (n, draw, blobs)")
+    if "n" not in sample:
+        raise ValueError("sample: the number of draws n is required")
+    n, draw, blobs = sample["n"], sample.get("draw", 0), sample.get("blobs")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= SAMPLE_MAX_N:
+        raise ValueError("sample: n must be an integer in 1 .. 2^31 - 1")
+    if isinstance(draw, bool) or not isinstance(draw, (int, np.integer)) or not 0 <= int(draw) <= _MASK32:
+        raise ValueError("sample: draw must be an integer in 0 .. 2^32 - 1")
+    if blobs not in (None, True, False):
+        raise ValueError("sample: blobs must be None, True or False")
+    return {"n": int(n), "draw": int(draw), "blobs": blobs}
+
+
+def make_sample(P, index, C, blobs, M, n_mass, n, draw):
+    """the record ``posterior_sample`` returns"""
+    return SimpleNamespace(P=P, index=np.asarray(index, dtype=np.int64), C=C, blobs=blobs, M=int(M), n_mass=int(n_mass), n=int(n),
+                           draw=int(draw))
+
+
+def engine_sample(eng, n, draw=0, blobs=None):
+    """``eng.posterior_sample(n, draw, blobs)`` for a PopulationEngine; any other engine object: the restatement on its result"""
+    if hasattr(eng, "posterior_sample"):
+        return eng.posterior_sample(n, draw=draw, blobs=blobs)
+    res = eng.result()
+    seed = eng.spec.seed
+    index, M, n_mass = sample_reference(res["P"], res.get("Wns"), n, seed, draw)
+    rb = res.get("blobs")
+    if blobs and rb is None:
+        raise ValueError("sample: blobs=True needs a simulator that returns blobs")
+    return make_sample(res["P"][index], index, res["C"][index], None if (rb is None or blobs is False) else rb[index], M, n_mass, n,
+                       draw)
+
+
 def summary_options(summary) -> dict:
     """the ``summary=`` keyword of the drivers: True, or a dict of cov / corrected / quantiles / wquantiles / hist"""
     if summary is True:

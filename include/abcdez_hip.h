@@ -469,6 +469,21 @@ ABCDEZ_API int abcdez_posterior_histograms(abcdez_ctx* ctx, const uint32_t* bits
                                            int32_t bins, const double* range, const int32_t* pairs, int32_t n_pairs,
                                            int32_t bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1, uint64_t* mass2,
                                            uint64_t* outside2, uint64_t* M, int64_t* n_mass);
+/*     posterior_sample (library version 650): n equally weighted draws from the weighted population -- what the reference's tests
+ *       build by hand as r.P[weightinds(r.Wns)] (test/runtests.jl:13-19) with the stratified resampler of src/abcdez_smc.jl:15-56 --
+ *       drawn and gathered on the device: abcdez_spec.h ("posterior summaries", POSTERIOR SAMPLE).  n strata (1 <= n <= 2^31 - 1, n <=
+ *       M; n need not be N) over the total integer mass, one point each from the RNG purpose ABZ_RNG_SAMPLE with epoch `draw`;
+ *       wns == NULL: unit masses, the closed form without a scan.  delta / stamp (device, N each; either may be NULL): the distances
+ *       and blob stamps to gather along.  Outputs, all DEVICE: idx_out[n] the drawn positions (non-decreasing), P_out[n][d] the
+ *       push_p-cast rows, dense; theta_out[n][ld] the internal rows (may be NULL; what abcdez_blob_eval takes); delta_out[n] and
+ *       stamp_out[n], NULL iff their source is.  HOST: *M the total mass, *n_mass the number of positions that count.  One
+ *       synchronisation.  Fails -- and then writes nothing to the outputs -- when no position carries mass, when the total mass
+ *       would reach 2^63, and when n > M.  It only reads the population; its scratch is the summaries' buffer, so a select enqueued
+ *       ahead and every other state of the context survive it: a run continued after it is bit-identical to one without it.    */
+ABCDEZ_API int abcdez_posterior_sample(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                       const double* wns, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
+                                       uint32_t* idx_out, double* P_out, double* theta_out, double* delta_out, uint64_t* stamp_out,
+                                       uint64_t* M, int64_t* n_mass);
 
 /* Test hooks: evaluate the spec arithmetic on the device (fn: 0 log, 1 exp, 2 sincos2pi,
  * 3 rint, 4 floor, 5 sqrt, 6 x/y2, 7 table log, 8 table sincos2pi, 9 sqrt_pn, 10 lgamma,

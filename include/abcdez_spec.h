@@ -116,7 +116,8 @@ enum {
   ABZ_RNG_SIM = 6,        /* simulator noise during sweeps                        */
   ABZ_RNG_BETTER = 7,     /* abcdemc "better particle" draw (mc:23)               */
   ABZ_RNG_STRATUM = 8,    /* stratified resampling uniform (smc:47)               */
-  ABZ_RNG_INIT_AUX = 9    /* rejection samplers of the Beta / NegativeBinomial priors */
+  ABZ_RNG_INIT_AUX = 9,   /* rejection samplers of the Beta / NegativeBinomial priors */
+  ABZ_RNG_SAMPLE = 10     /* word0 -> the point of a stratum of the posterior sample (idx = stratum, epoch = draw) */
 };
 
 typedef struct { uint64_t w0, w1; } abz_u64x2;
@@ -952,7 +953,35 @@ ABZ_HD double abz_tree_sum_small(const double* x, int p2) { /* p2 = power of two
  *   sum(mass2[pair]) + outside2[pair] == M.
  *   Limits: 1 <= bins <= 4096, 1 <= bins2 <= 128; pairs need d >= 2, two distinct requested columns and j < k; a pair is listed
  *   once.
- *   Sums of integers only: any order of accumulation (atomics included) gives the same bits. */
+ *   Sums of integers only: any order of accumulation (atomics included) gives the same bits.
+ *
+ * POSTERIOR SAMPLE (n equally weighted draws from the weighted population: what test/runtests.jl:13-19 builds by hand as
+ * r.P[weightinds(r.Wns)] with the stratified resampler of smc:15-56), in the same exact integers.  This text binds the implementations.
+ *   Random numbers: the purpose ABZ_RNG_SAMPLE.  No other stream is touched, so runs and checkpoints are what they were.
+ *   Mass and counting are those of the weighted quantiles and the histograms: m_i = abz_weight_fix(w_i, N), or 2^b for every position
+ *   with no weight array; a position counts iff m_i >= 1; M = sum m_i as an exact uint64, refused when it would reach 2^63, and when
+ *   n_mass = 0; the row of a position that does not count is never read.
+ *   Strata, for 1 <= n <= 2^31 - 1 and n <= M (anything else is refused): q = M div n, r = M mod n; stratum s < n starts at
+ *     a_s = s q + min(s, r)   and has the width   h_s = q + (s < r),       so that a_n = M: the strata tile [0, M).
+ *   Point of stratum s: R_s = a_s + ((u_s h_s) >> 64), u_s = word 0 of abz_rng(seed, s, draw, 0, ABZ_RNG_SAMPLE), the product being
+ *   the full 128 bits (abz_mulhi64: __umul64hi on the device, big integers in Python).  Nothing is divided, nothing rounds.
+ *   Index: idx_s = the smallest position i with C_i > R_s, C the inclusive sum of m in position order.  It exists because R_s < M,
+ *   and it counts (C_i > R_s >= C_i-1 needs m_i >= 1), so nothing is clamped.  The indices are non-decreasing in s: a user who needs
+ *   an exchangeable order shuffles them.
+ *   Row s of the sample is the push_p cast of the current row of position idx_s, i.e. r.P[idx_s]; distances (and blob stamps) are
+ *   gathered by the same index.
+ *   Unit masses (no weight array): C_i = (i + 1) 2^b, so idx_s = R_s >> b; an implementation takes this closed form, without a scan.
+ *   Consequences: position i covers m_i consecutive points of [0, M) and every stratum is q or q + 1 wide, so it is drawn at least
+ *   max(0, floor(m_i / (q + 1)) - 1) and at most ceil(m_i / q) + 1 times.  With equal masses m and n = k n_mass, q = floor(m / k).  When k divides m
+ *   (always for k = 1; for the unit masses 2^b whenever k is a power of two) r = 0, every counting position holds exactly k whole
+ *   strata and is drawn exactly k times; for k = 1 the sample is the identity over the counting positions.  When k does not divide m
+ *   the first r strata are one point wider, a stratum can straddle two positions, and only the two bounds above hold. */
+ABZ_HD uint64_t abz_sample_point(uint64_t seed, uint32_t s, uint32_t draw, uint64_t q, uint64_t r) {
+  const uint64_t a = (uint64_t)s * q + ((uint64_t)s < r ? (uint64_t)s : r);
+  const uint64_t h = q + ((uint64_t)s < r ? 1u : 0u);
+  return a + abz_mulhi64(abz_rng(seed, s, draw, 0, ABZ_RNG_SAMPLE).w0, h);
+}
+#define ABZ_SAMPLE_MAX_N 0x7FFFFFFFll
 #define ABZ_HIST_MAX_BINS 4096
 #define ABZ_HIST_MAX_BINS2 128
 /* the bin of x: 0 .. bins - 1, or bins (under), bins + 1 (over), bins + 2 (NaN) */

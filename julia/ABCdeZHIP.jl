@@ -548,6 +548,30 @@ function posterior_summary(e::Engine; packed::Bool=true, cov::Bool=true, correct
      wquantiles = wq, M = (isempty(wprobs) && hist === nothing) ? nothing : M[1],
      n_mass = (isempty(wprobs) && hist === nothing) ? nothing : Int(nmass[]), hist = h)
 end
+# ---- n equally weighted draws from the weighted population, drawn and gathered on the device (include/abcdez_spec.h "POSTERIOR
+# SAMPLE"; library version 650): what test/runtests.jl:13-19 builds as r.P[weightinds(r.Wns)], for any n.  Returns P (as `download`
+# shapes it), the 0-BASED positions `index` (non-decreasing: shuffle for an exchangeable order; P[s] is download's P[index[s] + 1]),
+# their distances C, the total integer mass M and n_mass.  packed = false: abcdemc's rows, unit masses.
+function posterior_sample(e::Engine; n::Integer, draw::Integer=0, packed::Bool=true)
+    ccall((:abcdez_version, LIB), Cint, ()) >= 650 || error("ABCdeZHIP: posterior_sample needs libabcdez_hip.so version 650 or later (rebuild the library)")
+    1 ≤ n ≤ typemax(Int32) || error("sample: n must be in 1 .. 2^31 - 1")
+    bits = packed ? e.bits[e.bc] : C_NULL; s0 = packed ? e.slot[1] : e.slot[e.cur]; s1 = packed ? e.slot[2] : C_NULL
+    w = packed ? e.wns : C_NULL
+    idx = devalloc(4n); P = devalloc(8 * n * e.d); Δo = devalloc(8n)
+    try
+        M = UInt64[0]; nmass = Ref(Int64(0))
+        check(ccall((:abcdez_posterior_sample, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}, Ptr{Cvoid},
+                     Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt64}, Ref{Int64}),
+                    e.ctx, bits, e.N, s0, s1, w, n, UInt32(draw), e.delta[e.cur], C_NULL, idx, P, C_NULL, Δo, C_NULL, M, nmass))
+        index = Vector{UInt32}(undef, n); th = Matrix{Float64}(undef, e.d, n); Δ = Vector{Float64}(undef, n)
+        d2h(e, index, idx, 4n); d2h(e, th, P, 8 * n * e.d); d2h(e, Δ, Δo, 8n)
+        Ps = e.d == 1 ? th[1, :] : [Tuple(th[:, i]) for i in 1:n]
+        return (P = Ps, index = Int64.(index), C = Δ, M = M[1], n_mass = Int(nmass[]), n = Int(n), draw = Int(draw))
+    finally
+        devfree(idx); devfree(P); devfree(Δo)
+    end
+end
 # the drivers' `summary` keyword: true, or a NamedTuple of the options above, e.g. (quantiles = [0.025, 0.975],)
 summary_of(e, summary; packed::Bool) = summary === nothing ? nothing :
     posterior_summary(e; packed = packed, (summary === true ? NamedTuple() : summary)...)
