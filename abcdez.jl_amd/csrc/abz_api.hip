@@ -12,6 +12,7 @@
 #include "../../include/abcdez_hip.h"
 #include <chrono>
 #include "abz_ctx.h"
+#include "abz_summary.h"
 
 int abz_tree_sum_impl(abcdez_ctx*, const double*, int64_t, int, double*);
 int abz_reweight_impl(abcdez_ctx*, const double*, double*, uint8_t*, int64_t, double, double, double*, double*, int64_t*);
@@ -1467,32 +1468,46 @@ int abcdez_push_p(abcdez_ctx* ctx, const double* theta, int64_t N, double* out) 
   return abz_launch_push_p(ctx, theta, N, out);
 }
 
+/* What the posterior calls check alike: the population arguments (`rest`: the call's other pointers that must not be null) -> the
+ * view the kernel files take, and the probabilities of the quantile calls. */
+static int posterior_pop(const char* call, abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                         const double* wns, bool rest, SumPop* p) {
+  const std::string who(call);
+  ABZ_REQUIRE(ctx && slot0 && rest, who + ": null argument");
+  ABZ_REQUIRE(!bits || slot1, who + ": packed storage (bits) needs both row slots");
+  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, who + ": N out of range");
+  *p = sum_pop(ctx, bits, N, slot0, slot1, wns);
+  return 0;
+}
+static int posterior_probs(const char* call, const double* probs, int32_t n_probs) {
+  const std::string who(call);
+  ABZ_REQUIRE(n_probs >= 1, who + ": n_probs must be at least 1");
+  for (int32_t q = 0; q < n_probs; ++q) ABZ_REQUIRE(probs[q] >= 0.0 && probs[q] <= 1.0, who + ": p must be in [0, 1]");
+  return 0;
+}
+
 /* Posterior summaries (csrc/abz_summary.hip).  Neither call touches a select enqueued ahead or the chain of asynchronous abcdemc
  * generations: they only read the population. */
 int abcdez_posterior_moments(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
                              const double* wns, int32_t want_second, double* mean, double* S, double* W, double* Q,
                              int64_t* n_pos) {
-  ABZ_REQUIRE(ctx && slot0 && mean && W && Q && n_pos, "posterior_moments: null argument");
-  ABZ_REQUIRE(!bits || slot1, "posterior_moments: packed storage (bits) needs both row slots");
+  SumPop p;
+  if (posterior_pop("posterior_moments", ctx, bits, N, slot0, slot1, wns, mean && W && Q && n_pos, &p)) return -1;
   ABZ_REQUIRE(!want_second || S, "posterior_moments: want_second without an array for S");
-  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_moments: N out of range");
-  return abz_posterior_moments_impl(ctx, bits, N, slot0, slot1, wns, want_second != 0, mean, S, W, Q, n_pos);
+  return abz_posterior_moments_impl(ctx, p, want_second != 0, mean, S, W, Q, n_pos);
 }
 
 int abcdez_posterior_quantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
                                const double* wns, int32_t k, const double* probs, int32_t n_probs, double* q_out) {
-  ABZ_REQUIRE(ctx && slot0 && probs && q_out, "posterior_quantiles: null argument");
-  ABZ_REQUIRE(!bits || slot1, "posterior_quantiles: packed storage (bits) needs both row slots");
-  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_quantiles: N out of range");
+  SumPop p;
+  if (posterior_pop("posterior_quantiles", ctx, bits, N, slot0, slot1, wns, probs && q_out, &p)) return -1;
   ABZ_REQUIRE(k >= 0 && k < ctx->h_model.d, "posterior_quantiles: k must be in 0 <= k < length(prior)");
-  ABZ_REQUIRE(n_probs >= 1, "posterior_quantiles: n_probs must be at least 1");
-  for (int32_t q = 0; q < n_probs; ++q)
-    ABZ_REQUIRE(probs[q] >= 0.0 && probs[q] <= 1.0, "posterior_quantiles: p must be in [0, 1]");
+  if (posterior_probs("posterior_quantiles", probs, n_probs)) return -1;
   /* the quantile is unweighted: it describes the posterior only where the positive weights are all equal */
   ABZ_REQUIRE(!wns || ctx->h_model.abck < ABZ_K_EPA,
               "posterior_quantiles: weighted quantiles are not provided (the Epanechnikov kernels give unequal weights; "
               "mean and covariance work for every kernel)");
-  return abz_posterior_quantiles_impl(ctx, bits, N, slot0, slot1, wns, k, probs, n_probs, q_out);
+  return abz_posterior_quantiles_impl(ctx, p, k, probs, n_probs, q_out);
 }
 
 /* Weighted marginal quantiles over the integer masses of the resampler (csrc/abz_wquantile.hip): every ABC kernel, with or
@@ -1500,15 +1515,12 @@ int abcdez_posterior_quantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N,
 int abcdez_posterior_wquantiles(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
                                 const double* wns, int32_t k0, int32_t nk, const double* probs, int32_t n_probs, double* q_out,
                                 uint64_t* M, int64_t* n_mass) {
-  ABZ_REQUIRE(ctx && slot0 && probs && q_out && M && n_mass, "posterior_wquantiles: null argument");
-  ABZ_REQUIRE(!bits || slot1, "posterior_wquantiles: packed storage (bits) needs both row slots");
-  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_wquantiles: N out of range");
+  SumPop p;
+  if (posterior_pop("posterior_wquantiles", ctx, bits, N, slot0, slot1, wns, probs && q_out && M && n_mass, &p)) return -1;
   ABZ_REQUIRE(nk >= 1 && k0 >= 0 && (int64_t)k0 + (int64_t)nk <= (int64_t)ctx->h_model.d,
               "posterior_wquantiles: the columns must be 0 <= k0, nk >= 1, k0 + nk <= length(prior)");
-  ABZ_REQUIRE(n_probs >= 1, "posterior_wquantiles: n_probs must be at least 1");
-  for (int32_t q = 0; q < n_probs; ++q)
-    ABZ_REQUIRE(probs[q] >= 0.0 && probs[q] <= 1.0, "posterior_wquantiles: p must be in [0, 1]");
-  return abz_posterior_wquantiles_impl(ctx, bits, N, slot0, slot1, wns, k0, nk, probs, n_probs, q_out, M, n_mass);
+  if (posterior_probs("posterior_wquantiles", probs, n_probs)) return -1;
+  return abz_posterior_wquantiles_impl(ctx, p, k0, nk, probs, n_probs, q_out, M, n_mass);
 }
 
 /* Marginal and pairwise histograms over the same integer masses (csrc/abz_hist.hip); like its neighbours it only reads the
@@ -1517,9 +1529,8 @@ int abcdez_posterior_histograms(abcdez_ctx* ctx, const uint32_t* bits, int64_t N
                                 const double* wns, const int32_t* cols, int32_t n_cols, int32_t bins, const double* range,
                                 const int32_t* pairs, int32_t n_pairs, int32_t bins2, double* lo_hi, uint64_t* mass1,
                                 uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass) {
-  ABZ_REQUIRE(ctx && slot0 && lo_hi && mass1 && tallies1 && M && n_mass, "posterior_histograms: null argument");
-  ABZ_REQUIRE(!bits || slot1, "posterior_histograms: packed storage (bits) needs both row slots");
-  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_histograms: N out of range");
+  SumPop p;
+  if (posterior_pop("posterior_histograms", ctx, bits, N, slot0, slot1, wns, lo_hi && mass1 && tallies1 && M && n_mass, &p)) return -1;
   const int32_t d = (int32_t)ctx->h_model.d;
   ABZ_REQUIRE(n_cols >= 1 && n_cols <= d, "posterior_histograms: the columns must be 1 <= n_cols <= length(prior)");
   std::vector<char> asked((size_t)d, 0);
@@ -1551,8 +1562,8 @@ int abcdez_posterior_histograms(abcdez_ctx* ctx, const uint32_t* bits, int64_t N
     std::sort(seen.begin(), seen.end());
     ABZ_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "posterior_histograms: a pair must not be listed twice");
   }
-  return abz_posterior_histograms_impl(ctx, bits, N, slot0, slot1, wns, cols, n_cols, bins, range, pairs, n_pairs, bins2, lo_hi, mass1,
-                                       tallies1, mass2, outside2, M, n_mass);
+  return abz_posterior_histograms_impl(ctx, p, cols, n_cols, bins, range, pairs, n_pairs, bins2, lo_hi, mass1, tallies1, mass2, outside2,
+                                       M, n_mass);
 }
 
 /* n equally weighted draws from the population and the gather of their rows, distances and stamps (csrc/abz_sample.hip); like its
@@ -1561,14 +1572,12 @@ int abcdez_posterior_sample(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, co
                             const double* wns, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
                             uint32_t* idx_out, double* P_out, double* theta_out, double* delta_out, uint64_t* stamp_out,
                             uint64_t* M, int64_t* n_mass) {
-  ABZ_REQUIRE(ctx && slot0 && idx_out && P_out && M && n_mass, "posterior_sample: null argument");
-  ABZ_REQUIRE(!bits || slot1, "posterior_sample: packed storage (bits) needs both row slots");
-  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, "posterior_sample: N out of range");
+  SumPop p;
+  if (posterior_pop("posterior_sample", ctx, bits, N, slot0, slot1, wns, idx_out && P_out && M && n_mass, &p)) return -1;
   ABZ_REQUIRE(n >= 1 && n <= ABZ_SAMPLE_MAX_N, "posterior_sample: n must be in 1 .. 2^31 - 1");
   ABZ_REQUIRE((delta != nullptr) == (delta_out != nullptr), "posterior_sample: delta_out is given iff delta is");
   ABZ_REQUIRE((stamp != nullptr) == (stamp_out != nullptr), "posterior_sample: stamp_out is given iff stamp is");
-  return abz_posterior_sample_impl(ctx, bits, N, slot0, slot1, wns, n, draw, delta, stamp, idx_out, P_out, theta_out, delta_out,
-                                   stamp_out, M, n_mass);
+  return abz_posterior_sample_impl(ctx, p, n, draw, delta, stamp, idx_out, P_out, theta_out, delta_out, stamp_out, M, n_mass);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

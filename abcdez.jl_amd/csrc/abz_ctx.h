@@ -339,19 +339,6 @@ int abz_launch_push_p(abcdez_ctx*, const double*, int64_t, double*);
 #define ABZ_SCAN_TILE 2048
 void abz_wfix_scan_enqueue(abcdez_ctx*, const double* wns, uint32_t n, unsigned long long* tile, uint32_t* tile_lp,
                            unsigned long long* last_pos, unsigned long long* cum);
-int abz_posterior_moments_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
-                               int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
-int abz_posterior_quantiles_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
-                                 int k, const double* probs, int n_probs, double* q_out);
-int abz_posterior_wquantiles_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
-                                  int k0, int nk, const double* probs, int n_probs, double* q_out, uint64_t* M, int64_t* n_mass);
-int abz_posterior_sample_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
-                              int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp, uint32_t* idx_out, double* P_out,
-                              double* theta_out, double* delta_out, uint64_t* stamp_out, uint64_t* M, int64_t* n_mass);
-int abz_posterior_histograms_impl(abcdez_ctx*, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
-                                  const int32_t* cols, int n_cols, int bins, const double* range, const int32_t* pairs, int n_pairs,
-                                  int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2,
-                                  uint64_t* M, int64_t* n_mass);
 void abz_fold_counters(abcdez_ctx*);
 /* Read-back of the first `nwords` device scalars WITHOUT the copy engine and without a stream synchronisation: a one-block
  * kernel writes them straight into the pinned host mirror and stores a sequence word last (system-scope release); the

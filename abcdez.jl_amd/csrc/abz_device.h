@@ -582,6 +582,10 @@ __device__ inline void block_count2(unsigned int x, unsigned int y, unsigned lon
   }
 }
 
+/* the current slot of position p in packed storage: 32 positions per word (the index arithmetic stays in the caller's type) */
+template <class I>
+__device__ inline uint32_t packed_bit(const uint32_t* __restrict__ bits, I p) { return (bits[p >> 5] >> (uint32_t)(p & 31)) & 1u; }
+
 /* order-preserving u64 image of a double (negative values, -0.0 included, sort below the positive ones) */
 __device__ inline unsigned long long f64_order_key(double x) {
   const unsigned long long u = abz_d2u(x);

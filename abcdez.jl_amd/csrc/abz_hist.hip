@@ -45,24 +45,6 @@ typedef unsigned long long u64;
 struct HistCol { double lo, hi, scale, scale2; int32_t col, pad; };
 struct HistBatch { int32_t cj, n, r0, r1; int32_t ck[HB_K]; int32_t pair[HB_K]; };
 
-__device__ inline u64 hist_key(double v) {
-  const u64 u = abz_d2u(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ inline double hist_value(u64 key) { return abz_u2d((key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key); }
-__device__ inline u64 hist_wave_sum(u64 v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ inline u64 hist_mass(const SumPop& p, int64_t i, int b) {
-  return p.wns ? abz_weight_fix(p.wns[i], (uint32_t)p.N) : (1ull << b);
-}
-__device__ inline const double* hist_row(const SumPop& p, int64_t i) {
-  const uint32_t bit = p.bits ? (p.bits[i >> 5] >> (uint32_t)(i & 31)) & 1u : 0u;
-  return (bit ? p.slot1 : p.slot0) + (size_t)i * (size_t)p.ld;
-}
-
 /* ---- range: krange[2 c + {0, 1}] = (smallest, largest) order key of requested column c over the counting positions, for the
  * columns c0 .. c0 + ncols - 1 of the list */
 __global__ __launch_bounds__(ABZ_BLOCK) void hist_range_kernel(const abz_model* __restrict__ M, const SumPop p,
@@ -79,14 +61,14 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_range_kernel(const abz_model* 
   const int b = abz_stratum_bits((uint32_t)p.N);
   bool any = false;
   for (int64_t i = (int64_t)blockIdx.x * ABZ_BLOCK + t; i < p.N; i += (int64_t)gridDim.x * ABZ_BLOCK) {
-    if (hist_mass(p, i, b) < 1) continue;
+    if (sum_mass(p, i, b) < 1) continue;
     any = true;
-    const double* row = hist_row(p, i);
+    const double* row = sum_row(p, i);
 #pragma unroll
     for (int c = 0; c < H_RC; ++c) {
       if (c < ncols) {
         const int col = s_col[c];
-        const u64 key = hist_key(abz_push_p(&M->prior[col], row[col]));
+        const u64 key = f64_order_key(abz_push_p(&M->prior[col], row[col]));
         if (key < kmin[c]) kmin[c] = key;
         if (key > kmax[c]) kmax[c] = key;
       }
@@ -111,8 +93,8 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_setup_kernel(HistCol* __restri
   for (int c = threadIdx.x; c < nc; c += ABZ_BLOCK) {
     double lo = cols[c].lo, hi = cols[c].hi;
     if (automatic) {
-      lo = hist_value(krange[2 * c]);
-      hi = hist_value(krange[2 * c + 1]);
+      lo = f64_from_order_key_dev(krange[2 * c]);
+      hi = f64_from_order_key_dev(krange[2 * c + 1]);
       if (lo == hi) { lo = lo - 0.5; hi = hi + 0.5; }
       const double w = hi - lo;
       const double big = 0x1.fffffffffffffp1023;
@@ -132,18 +114,15 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_bin_kernel(const abz_model* __
                                                             const HistCol* __restrict__ cols, int nc, int bins, int bins2,
                                                             int64_t Nld, u64* __restrict__ mass, uint16_t* __restrict__ idx1,
                                                             uint8_t* __restrict__ idx2, u64* __restrict__ tot) {
-  __shared__ u64 s_tot[3];
   const int t = threadIdx.x;
-  if (t < 3) s_tot[t] = 0ull;
-  __syncthreads();
   u64 lo = 0, hi = 0, cnt = 0;
   const int b = abz_stratum_bits((uint32_t)p.N);
   for (int64_t i = (int64_t)blockIdx.x * ABZ_BLOCK + t; i < Nld; i += (int64_t)gridDim.x * ABZ_BLOCK) {
-    const u64 m = i < p.N ? hist_mass(p, i, b) : 0ull;
+    const u64 m = i < p.N ? sum_mass(p, i, b) : 0ull;
     mass[i] = m;
     if (m < 1) continue;
     lo += m & 0xFFFFFFFFull; hi += m >> 32; cnt += 1;
-    const double* row = hist_row(p, i);
+    const double* row = sum_row(p, i);
     for (int c = 0; c < nc; ++c) {
       const HistCol h = cols[c];
       const double x = abz_push_p(&M->prior[h.col], row[h.col]);
@@ -154,10 +133,7 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_bin_kernel(const abz_model* __
       }
     }
   }
-  lo = hist_wave_sum(lo); hi = hist_wave_sum(hi); cnt = hist_wave_sum(cnt);
-  if ((t & 63) == 0 && cnt) { atomicAdd(&s_tot[0], lo); atomicAdd(&s_tot[1], hi); atomicAdd(&s_tot[2], cnt); }
-  __syncthreads();
-  if (t < 3 && s_tot[2]) atomicAdd(&tot[t], s_tot[t]);
+  sum_mass_tally(lo, hi, cnt, tot);
 }
 
 /* the four masses of a thread's positions i .. i + 3 (i a multiple of 4, the array 16-byte aligned) */
@@ -269,11 +245,11 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_pair_kernel(const u64* __restr
 }
 
 /* ================================================================ host side */
-int abz_posterior_histograms_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
-                                  const double* wns, const int32_t* cols, int nc, int bins, const double* range,
+int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_t* cols, int nc, int bins, const double* range,
                                   const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
                                   uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
-  const int d = ctx->h_model.d;
+  const int64_t N = p.N;
+  const int d = p.d;
   /* the blob the host uploads: [ columns | key ranges | batches ] */
   std::vector<int> pos((size_t)d, -1);
   std::vector<HistCol> hc((size_t)nc);
@@ -336,7 +312,6 @@ int abz_posterior_histograms_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t
   u64* mass = (u64*)(base + o_mass);
   uint16_t* idx1 = (uint16_t*)(base + o_idx1);
   uint8_t* idx2 = n_pairs > 0 ? (uint8_t*)(base + o_idx2) : nullptr;
-  const SumPop p = sum_pop(ctx, bits, N, slot0, slot1, wns);
   const abz_model* dm = (const abz_model*)ctx->d_model;
 
   ABZ_HIP_CHECK(hipMemsetAsync(base, 0, o_blob, ctx->stream));
@@ -379,21 +354,17 @@ int abz_posterior_histograms_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t
   ABZ_HIP_CHECK(hipMemcpyAsync(h.data(), base, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (n_m2) ABZ_HIP_CHECK(hipMemcpyAsync(mass2, m2, n_m2 * 8, hipMemcpyDeviceToHost, ctx->stream));
   ABZ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (h[2] < 1) { abz_set_error("posterior_histograms: no particle has a positive weight that carries mass"); return -1; }
-  const unsigned __int128 Mfull = ((unsigned __int128)h[1] << 32) + (unsigned __int128)h[0];
-  if (Mfull >= ((unsigned __int128)1 << 63)) {
-    abz_set_error("posterior_histograms: the total mass reaches 2^63 -- the weights are not normalised (sum(Wns) must be about 1)");
-    return -1;
-  }
+  uint64_t Mv = 0;
+  int64_t nm = 0;
+  if (sum_mass_verdict("posterior_histograms", h[0], h[1], h[2], &Mv, &nm)) return -1;
   if (h[3]) {
     const int c = nc - (int)h[3];
     abz_set_error("posterior_histograms: the automatic range of column " + std::to_string(hc[c].col) +
                   " is not usable (a NaN or an infinity among the counting rows, or hi - lo not finite): pass a range");
     return -1;
   }
-  const uint64_t Mv = (uint64_t)Mfull;
   *M_out = Mv;
-  *n_mass = (int64_t)h[2];
+  *n_mass = nm;
   memcpy(lo_hi, h.data() + o_lohi / 8, (size_t)nc * 16);
   for (int c = 0; c < nc; ++c) {
     const u64* src = h.data() + o_m1 / 8 + (size_t)c * (size_t)stride;

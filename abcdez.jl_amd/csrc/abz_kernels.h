@@ -115,8 +115,6 @@ struct SmcPackedArgs {
   uint32_t rev;                 /* non-zero: workgroup b owns tile gridDim.x - 1 - b (serpentine order, abz_smc_swarm.hip) */
 };
 
-__device__ inline uint32_t packed_bit(const uint32_t* __restrict__ bits, uint32_t p) { return (bits[p >> 5] >> (p & 31u)) & 1u; }
-
 template <int SIM, int L, int C, bool PLAIN = false>
 __device__ inline void smc_swarm_packed_body_1p(const SmcPackedArgs& a) {
   constexpr int LD = L * C;

@@ -36,22 +36,12 @@ enum { SMP_OK = 0, SMP_TOO_HEAVY = 1, SMP_NO_MASS = 2, SMP_TOO_MANY = 3 };
 
 /* ---- count: hdr[LO] += low halves, hdr[HI] += high halves of the masses, hdr[NMASS] += #(m >= 1) */
 __global__ __launch_bounds__(ABZ_BLOCK) void sample_count_kernel(const double* __restrict__ wns, uint32_t N, u64* __restrict__ hdr) {
-  __shared__ u64 s_tot[3];
-  const int t = threadIdx.x;
-  if (t < 3) s_tot[t] = 0ull;
-  __syncthreads();
   u64 lo = 0, hi = 0, cnt = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * ABZ_BLOCK + t; i < N; i += (uint64_t)gridDim.x * ABZ_BLOCK) {
+  for (uint64_t i = (uint64_t)blockIdx.x * ABZ_BLOCK + threadIdx.x; i < N; i += (uint64_t)gridDim.x * ABZ_BLOCK) {
     const u64 m = abz_weight_fix(wns[i], N);
     lo += m & 0xFFFFFFFFull; hi += m >> 32; cnt += m ? 1u : 0u;
   }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    lo += __shfl_xor(lo, off, 64); hi += __shfl_xor(hi, off, 64); cnt += __shfl_xor(cnt, off, 64);
-  }
-  if ((t & 63) == 0 && cnt) { atomicAdd(&s_tot[0], lo); atomicAdd(&s_tot[1], hi); atomicAdd(&s_tot[2], cnt); }
-  __syncthreads();
-  if (t < 3 && s_tot[2]) atomicAdd(&hdr[t], s_tot[t]);
+  sum_mass_tally(lo, hi, cnt, hdr);
 }
 
 /* ---- setup: M, q, r and the flag.  unit_b >= 0: no weight array, every position has the mass 2^unit_b */
@@ -59,16 +49,11 @@ __global__ void sample_setup_kernel(u64* __restrict__ hdr, uint32_t N, u64 n, in
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   u64 lo = hdr[SMP_H_LO], hi = hdr[SMP_H_HI], n_mass = hdr[SMP_H_NMASS];
   if (unit_b >= 0) { lo = 0; hi = (u64)N << (unit_b - 32); n_mass = N; }     /* b >= 32 for every N < 2^31: N 2^b as its high half */
-  /* M = hi 2^32 + lo; both sums of fewer than 2^31 halves below 2^32 are exact: M >= 2^63 iff hi + (lo >> 32) reaches 2^31 */
-  const u64 top = hi + (lo >> 32);
   u64 flag = SMP_OK, M = 0, q = 0, r = 0;
   if (n_mass < 1) flag = SMP_NO_MASS;
-  else if (top >= (1ull << 31)) flag = SMP_TOO_HEAVY;
-  else {
-    M = (top << 32) | (lo & 0xFFFFFFFFull);
-    if (n > M) flag = SMP_TOO_MANY;
-    else { q = M / n; r = M % n; }
-  }
+  else if (!sum_mass_total(lo, hi, &M)) flag = SMP_TOO_HEAVY;
+  else if (n > M) flag = SMP_TOO_MANY;
+  else { q = M / n; r = M % n; }
   hdr[SMP_H_NMASS] = n_mass; hdr[SMP_H_M] = M; hdr[SMP_H_Q] = q; hdr[SMP_H_R] = r; hdr[SMP_H_FLAG] = flag;
 }
 
@@ -115,8 +100,7 @@ __global__ __launch_bounds__(ABZ_BLOCK) void sample_gather_kernel(const abz_mode
   if (s >= n) return;
   const uint32_t src = idx[s];
   if (src >= (uint64_t)p.N) return;
-  const uint32_t bit = p.bits ? (p.bits[src >> 5] >> (src & 31u)) & 1u : 0u;
-  const double* __restrict__ row = (bit ? p.slot1 : p.slot0) + (size_t)src * (size_t)p.ld;
+  const double* __restrict__ row = sum_row(p, src);
   double* __restrict__ po = P_out + (size_t)s * (size_t)p.d;
   double* __restrict__ to = theta_out ? theta_out + (size_t)s * (size_t)p.ld : nullptr;
   if (p.ld == 1) {
@@ -138,19 +122,19 @@ __global__ __launch_bounds__(ABZ_BLOCK) void sample_gather_kernel(const abz_mode
 }
 
 /* ================================================================ host side */
-int abz_posterior_sample_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
-                              const double* wns, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
+int abz_posterior_sample_impl(abcdez_ctx* ctx, const SumPop& p, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
                               uint32_t* idx_out, double* P_out, double* theta_out, double* delta_out, uint64_t* stamp_out,
                               uint64_t* M_out, int64_t* n_mass) {
-  const uint32_t Nu = (uint32_t)N, nu = (uint32_t)n;
+  const double* wns = p.wns;
+  const uint32_t Nu = (uint32_t)p.N, nu = (uint32_t)n;
   const int b = abz_stratum_bits(Nu);
   if (!wns) {                              /* everything is known here: refuse before anything is enqueued */
-    const unsigned __int128 Mfull = (unsigned __int128)Nu << b;
-    if (Mfull >= ((unsigned __int128)1 << 63)) {
-      abz_set_error("posterior_sample: the total mass reaches 2^63 (N 2^b with N = " + std::to_string((long long)N) + ")");
+    u64 M = 0;
+    if (!sum_mass_total(0, (u64)Nu << (b - 32), &M)) {               /* N 2^b as its high half, as in sample_setup_kernel */
+      abz_set_error("posterior_sample: the total mass reaches 2^63 (N 2^b with N = " + std::to_string((long long)p.N) + ")");
       return -1;
     }
-    if ((unsigned __int128)n > Mfull) { abz_set_error("posterior_sample: n exceeds the total mass M"); return -1; }
+    if ((u64)n > M) { abz_set_error("posterior_sample: n exceeds the total mass M"); return -1; }
   }
   const uint32_t nt = (Nu + ABZ_SCAN_TILE - 1) / ABZ_SCAN_TILE;
   /* [ header | last_pos || tile offsets | tile_lp | C ]: only the header is zeroed and read back */
@@ -164,7 +148,6 @@ int abz_posterior_sample_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, 
   u64* tile = (u64*)(base + o_tile);
   uint32_t* tile_lp = (uint32_t*)(base + o_lp);
   u64* cum = wns ? (u64*)(base + o_cum) : nullptr;
-  const SumPop p = sum_pop(ctx, bits, N, slot0, slot1, wns);
 
   ABZ_HIP_CHECK(hipMemsetAsync(base, 0, o_tile, ctx->stream));
   if (wns) {
@@ -187,10 +170,8 @@ int abz_posterior_sample_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, 
   ABZ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   switch (h[SMP_H_FLAG]) {
     case SMP_OK: break;
-    case SMP_NO_MASS: abz_set_error("posterior_sample: no particle has a positive weight that carries mass"); return -1;
-    case SMP_TOO_HEAVY:
-      abz_set_error("posterior_sample: the total mass reaches 2^63 -- the weights are not normalised (sum(Wns) must be about 1)");
-      return -1;
+    case SMP_NO_MASS: return sum_mass_refuse("posterior_sample", false);
+    case SMP_TOO_HEAVY: return sum_mass_refuse("posterior_sample", true);
     default: abz_set_error("posterior_sample: n exceeds the total mass M"); return -1;
   }
   *M_out = h[SMP_H_M];

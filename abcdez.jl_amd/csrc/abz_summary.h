@@ -1,7 +1,9 @@
-/* abz_summary.h -- what the posterior-summary translation units share (abz_summary.hip, abz_wquantile.hip): the view of a
- * population and the calls' buffer in the context. */
+/* abz_summary.h -- what the posterior calls share (abz_summary.hip, abz_wquantile.hip, abz_hist.hip, abz_sample.hip and their
+ * entry points in abz_api.hip): the view of a population, the current row and the integer mass of a position, the tally of the
+ * masses and its verdict, and the calls' buffer in the context. */
 #pragma once
 #include "abz_ctx.h"
+#include "abz_device.h"
 
 struct SumPop {
   const uint32_t* bits;     /* NULL: classic storage, slot0 is the row array */
@@ -19,5 +21,60 @@ static inline SumPop sum_pop(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, c
   return p;
 }
 
-/* ctx->sum_ws holds at least `bytes` afterwards (abz_summary.hip); the contents do not survive a growth */
+/* ---- device side */
+/* the current row of position i: the slot its bit names */
+__device__ inline const double* sum_row(const SumPop& p, int64_t i) {
+  const uint32_t b = p.bits ? packed_bit(p.bits, i) : 0u;
+  return (b ? p.slot1 : p.slot0) + (size_t)i * (size_t)p.ld;
+}
+/* the integer mass of position i, b = abz_stratum_bits(N): the resampler's fixed point, or 2^b each without weights */
+__device__ inline unsigned long long sum_mass(const SumPop& p, int64_t i, int b) {
+  return p.wns ? abz_weight_fix(p.wns[i], (uint32_t)p.N) : (1ull << b);
+}
+/* every lane gets the sum over its wavefront */
+__device__ inline unsigned long long sum_wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+/* block tally of the masses: every thread brings the low halves, the high halves and the number of its masses >= 1; wave sums ->
+ * LDS -> one global atomic per block and word, tot[0] += low halves, tot[1] += high halves, tot[2] += n_mass, when the block
+ * counted anything.  Both sums of fewer than 2^31 halves below 2^32 are exact.  Must be reached by every thread of the block. */
+__device__ inline void sum_mass_tally(unsigned long long lo, unsigned long long hi, unsigned long long cnt,
+                                      unsigned long long* __restrict__ tot) {
+  __shared__ unsigned long long s_tot[3];
+  const int t = threadIdx.x;
+  if (t < 3) s_tot[t] = 0ull;
+  __syncthreads();
+  lo = sum_wave_sum_u64(lo); hi = sum_wave_sum_u64(hi); cnt = sum_wave_sum_u64(cnt);
+  if ((t & 63) == 0 && cnt) { atomicAdd(&s_tot[0], lo); atomicAdd(&s_tot[1], hi); atomicAdd(&s_tot[2], cnt); }
+  __syncthreads();
+  if (t < 3 && s_tot[2]) atomicAdd(&tot[t], s_tot[t]);
+}
+/* M = hi 2^32 + lo from the tally; false: M reaches 2^63, which is the case iff hi + (lo >> 32) reaches 2^31 */
+__host__ __device__ inline bool sum_mass_total(unsigned long long lo, unsigned long long hi, unsigned long long* M) {
+  const unsigned long long top = hi + (lo >> 32);
+  if (top >= (1ull << 31)) return false;
+  *M = (top << 32) | (lo & 0xFFFFFFFFull);
+  return true;
+}
+
+/* ---- host side (abz_summary.hip) */
+/* ctx->sum_ws holds at least `bytes` afterwards; the contents do not survive a growth */
 int sum_ws_reserve(abcdez_ctx* ctx, size_t bytes);
+/* the two refusals of the totals under the name of `call` (no mass, or M reaches 2^63): sets the error and returns -1 */
+int sum_mass_refuse(const char* call, bool too_heavy);
+/* the verdict on a tally: fills *M_out and *n_mass, or refuses */
+int sum_mass_verdict(const char* call, unsigned long long lo, unsigned long long hi, unsigned long long cnt, uint64_t* M_out,
+                     int64_t* n_mass);
+
+int abz_posterior_moments_impl(abcdez_ctx*, const SumPop&, int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
+int abz_posterior_quantiles_impl(abcdez_ctx*, const SumPop&, int k, const double* probs, int n_probs, double* q_out);
+int abz_posterior_wquantiles_impl(abcdez_ctx*, const SumPop&, int k0, int nk, const double* probs, int n_probs, double* q_out, uint64_t* M,
+                                  int64_t* n_mass);
+int abz_posterior_histograms_impl(abcdez_ctx*, const SumPop&, const int32_t* cols, int n_cols, int bins, const double* range,
+                                  const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
+                                  uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass);
+int abz_posterior_sample_impl(abcdez_ctx*, const SumPop&, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
+                              uint32_t* idx_out, double* P_out, double* theta_out, double* delta_out, uint64_t* stamp_out, uint64_t* M,
+                              int64_t* n_mass);

@@ -19,6 +19,7 @@
  */
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "abz_ctx.h"
@@ -44,10 +45,7 @@ __device__ inline int sum_owned(const SumPop& p, int64_t base, double (&w)[8], c
     const bool live = wv > 0.0;
     w[q] = live ? wv : 0.0;
     row[q] = nullptr;
-    if (live) {
-      const uint32_t b = p.bits ? (p.bits[i >> 5] >> (uint32_t)(i & 31)) & 1u : 0u;
-      row[q] = (b ? p.slot1 : p.slot0) + (size_t)i * (size_t)p.ld;
-    }
+    if (live) row[q] = sum_row(p, i);
     c += live;
   }
   return c;
@@ -68,9 +66,7 @@ __global__ __launch_bounds__(ABZ_BLOCK) void sum_first_kernel(const abz_model* _
   const int64_t nt = gridDim.x, tile = blockIdx.x;
   double w[8];
   const double* row[8];
-  unsigned long long c = (unsigned long long)sum_owned(p, tile * ABZ_TILE, w, row);
-#pragma unroll
-  for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off, 64);
+  const unsigned long long c = sum_wave_sum_u64((unsigned long long)sum_owned(p, tile * ABZ_TILE, w, row));
   if ((t & 63) == 0 && c) atomicAdd(n_pos, c);
   {
     double e[8];
@@ -220,16 +216,11 @@ __global__ __launch_bounds__(ABZ_BLOCK) void sum_column_kernel(const abz_model* 
   if (i < p.N) {
     live = (p.wns ? p.wns[i] : 1.0) > 0.0;
     double v = 0.0;
-    if (live) {
-      const uint32_t b = p.bits ? (p.bits[i >> 5] >> (uint32_t)(i & 31)) & 1u : 0u;
-      v = abz_push_p(&M->prior[k], ((b ? p.slot1 : p.slot0) + (size_t)i * (size_t)p.ld)[k]);
-    }
+    if (live) v = abz_push_p(&M->prior[k], sum_row(p, i)[k]);
     col[i] = v;
     mask[i] = (uint8_t)live;
   }
-  unsigned long long c = live;
-#pragma unroll
-  for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off, 64);
+  const unsigned long long c = sum_wave_sum_u64(live);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_pos, c);
 }
 
@@ -244,9 +235,25 @@ int sum_ws_reserve(abcdez_ctx* ctx, size_t bytes) {
   ctx->sum_ws_bytes = want;
   return 0;
 }
-int abz_posterior_moments_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
-                               const double* wns, int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos) {
-  const int d = ctx->h_model.d;
+int sum_mass_refuse(const char* call, bool too_heavy) {
+  abz_set_error(std::string(call) + (too_heavy ? ": the total mass reaches 2^63 -- the weights are not normalised (sum(Wns) must be about 1)"
+                                               : ": no particle has a positive weight that carries mass"));
+  return -1;
+}
+int sum_mass_verdict(const char* call, unsigned long long lo, unsigned long long hi, unsigned long long cnt, uint64_t* M_out,
+                     int64_t* n_mass) {
+  unsigned long long M = 0;
+  if (cnt < 1) return sum_mass_refuse(call, false);
+  if (!sum_mass_total(lo, hi, &M)) return sum_mass_refuse(call, true);
+  *M_out = M;
+  *n_mass = (int64_t)cnt;
+  return 0;
+}
+
+int abz_posterior_moments_impl(abcdez_ctx* ctx, const SumPop& p, int want_second, double* mean, double* S, double* W, double* Q,
+                               int64_t* n_pos) {
+  const int64_t N = p.N;
+  const int d = p.d;
   const size_t nt = (size_t)((N + ABZ_TILE - 1) / ABZ_TILE);
   const size_t npairs = (size_t)d * (size_t)(d + 1) / 2;
   const size_t ntrees = want_second && npairs > (size_t)d + 2 ? npairs : (size_t)d + 2;
@@ -259,7 +266,6 @@ int abz_posterior_moments_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N,
   double* res1 = (double*)(base + o_res1);
   double* res2 = (double*)(base + o_res2);
   double* parts = (double*)(base + o_parts);
-  const SumPop p = sum_pop(ctx, bits, N, slot0, slot1, wns);
 
   ABZ_HIP_CHECK(hipMemsetAsync(d_npos, 0, 8, ctx->stream));
   hipLaunchKernelGGL(sum_first_kernel, dim3((unsigned)nt), dim3(ABZ_BLOCK), 0, ctx->stream, (const abz_model*)ctx->d_model, p, parts, d_npos);
@@ -290,8 +296,8 @@ int abz_posterior_moments_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N,
   return 0;
 }
 
-int abz_posterior_quantiles_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
-                                 const double* wns, int k, const double* probs, int n_probs, double* q_out) {
+int abz_posterior_quantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k, const double* probs, int n_probs, double* q_out) {
+  const int64_t N = p.N;
   /* [ n_pos | column N x f64 | mask N x u8 ] */
   const size_t o_col = 256, o_mask = o_col + abz_align((size_t)N * 8);
   int rc = sum_ws_reserve(ctx, o_mask + abz_align((size_t)N));
@@ -300,7 +306,6 @@ int abz_posterior_quantiles_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t 
   unsigned long long* d_npos = (unsigned long long*)base;
   double* col = (double*)(base + o_col);
   uint8_t* mask = (uint8_t*)(base + o_mask);
-  const SumPop p = sum_pop(ctx, bits, N, slot0, slot1, wns);
   ABZ_HIP_CHECK(hipMemsetAsync(d_npos, 0, 8, ctx->stream));
   hipLaunchKernelGGL(sum_column_kernel, dim3((unsigned)((N + ABZ_BLOCK - 1) / ABZ_BLOCK)), dim3(ABZ_BLOCK), 0, ctx->stream,
                      (const abz_model*)ctx->d_model, p, k, col, mask, d_npos);

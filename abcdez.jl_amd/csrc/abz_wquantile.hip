@@ -48,57 +48,41 @@ struct WqState {            /* one per column of the chunk */
 
 struct WqProbs { double p[WQ_PB]; int n; };
 
-__device__ inline u64 wq_key(double v) {
-  const u64 u = abz_d2u(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ inline double wq_value(u64 key) { return abz_u2d((key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key); }
-__device__ inline u64 wq_wave_sum(u64 v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 /* ---- gather: keys[c N + i] for the counting positions (others are never read: their mass is 0), mass[i], the totals
  * tot[0] = sum of the low 32 bits of the masses, tot[1] = sum of the high 32 bits, tot[2] = n_mass (first chunk only), and
  * parts[(c nb + block) 3 + {0, 1, 2}] = (smallest key, smallest mass at it, largest key) of the block's positions */
 __global__ __launch_bounds__(ABZ_BLOCK) void wq_gather_kernel(const abz_model* __restrict__ M, const SumPop p, int k_first, int ncols,
                                                              u64* __restrict__ keys, u64* __restrict__ mass, int first_chunk,
                                                              u64* __restrict__ parts, u64* __restrict__ tot) {
-  __shared__ u64 s_kmin[WQ_CB], s_m1[WQ_CB], s_kmax[WQ_CB], s_tot[3];
+  __shared__ u64 s_kmin[WQ_CB], s_m1[WQ_CB], s_kmax[WQ_CB];
   const int t = threadIdx.x;
   u64 kmin[WQ_CB], m1[WQ_CB], kmax[WQ_CB];
 #pragma unroll
   for (int c = 0; c < WQ_CB; ++c) { kmin[c] = ~0ull; m1[c] = ~0ull; kmax[c] = 0ull; }
   if (t < WQ_CB) { s_kmin[t] = ~0ull; s_m1[t] = ~0ull; s_kmax[t] = 0ull; }
-  if (t < 3) s_tot[t] = 0ull;
   u64 lo = 0, hi = 0, cnt = 0;
   const int b = abz_stratum_bits((uint32_t)p.N);
   for (int64_t i = (int64_t)blockIdx.x * ABZ_BLOCK + t; i < p.N; i += (int64_t)gridDim.x * ABZ_BLOCK) {
-    const u64 m = p.wns ? abz_weight_fix(p.wns[i], (uint32_t)p.N) : (1ull << b);
+    const u64 m = sum_mass(p, i, b);
     if (first_chunk) mass[i] = m;
     if (m < 1) continue;
     lo += m & 0xFFFFFFFFull; hi += m >> 32; cnt += 1;
-    const uint32_t bit = p.bits ? (p.bits[i >> 5] >> (uint32_t)(i & 31)) & 1u : 0u;
-    const double* row = (bit ? p.slot1 : p.slot0) + (size_t)i * (size_t)p.ld + k_first;
+    const double* row = sum_row(p, i) + k_first;
 #pragma unroll
     for (int c = 0; c < WQ_CB; ++c) {
       if (c < ncols) {
-        const u64 key = wq_key(abz_push_p(&M->prior[k_first + c], row[c]));
+        const u64 key = f64_order_key(abz_push_p(&M->prior[k_first + c], row[c]));
         keys[(size_t)c * (size_t)p.N + (size_t)i] = key;
         if (key < kmin[c] || (key == kmin[c] && m < m1[c])) { kmin[c] = key; m1[c] = m; }
         if (key > kmax[c]) kmax[c] = key;
       }
     }
   }
+  if (first_chunk) sum_mass_tally(lo, hi, cnt, tot);                   /* kernel-uniform */
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < WQ_CB; ++c) {
     if (c < ncols && cnt) { atomicMin(&s_kmin[c], kmin[c]); atomicMax(&s_kmax[c], kmax[c]); }
-  }
-  if (first_chunk) {
-    lo = wq_wave_sum(lo); hi = wq_wave_sum(hi); cnt = wq_wave_sum(cnt);
-    if ((t & 63) == 0 && cnt) { atomicAdd(&s_tot[0], lo); atomicAdd(&s_tot[1], hi); atomicAdd(&s_tot[2], cnt); }
   }
   __syncthreads();
 #pragma unroll
@@ -110,7 +94,6 @@ __global__ __launch_bounds__(ABZ_BLOCK) void wq_gather_kernel(const abz_model* _
     u64* o = parts + ((size_t)t * gridDim.x + blockIdx.x) * 3;
     o[0] = s_kmin[t]; o[1] = s_m1[t]; o[2] = s_kmax[t];
   }
-  if (first_chunk && t < 3 && s_tot[2]) atomicAdd(&tot[t], s_tot[t]);
 }
 
 /* ---- targets: one block per column.  (v_1, m_(1), v_n) from the blocks' partials, then per probability
@@ -298,25 +281,25 @@ __global__ void wq_final_kernel(const WqState* __restrict__ st, int np, double* 
   if (t >= np) return;
   double q;
   if (s->top[t]) {
-    q = wq_value(s->kmax);
+    q = f64_from_order_key_dev(s->kmax);
   } else {
     const int slot = s->slot_of[t];
-    const double vk = wq_value(s->prefix[slot]);
+    const double vk = f64_from_order_key_dev(s->prefix[slot]);
     const u64 hb = s->hrem[t], mm = s->mmin[slot];
     if (hb >= mm) {                                   /* the crossing is not in the first element of the tie group: v_k-1 = v_k */
       q = abz_quantile_type7(vk, vk, 0.0);
     } else {
       const double g = (double)hb / (double)mm;
-      q = abz_quantile_type7(wq_value(s->vprev[slot]), vk, g);
+      q = abz_quantile_type7(f64_from_order_key_dev(s->vprev[slot]), vk, g);
     }
   }
   res[(size_t)c * n_total + q0 + t] = q;
 }
 
 /* ================================================================ host side */
-int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
-                                  const double* wns, int k0, int nk, const double* probs, int n_probs, double* q_out, uint64_t* M_out,
-                                  int64_t* n_mass) {
+int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k0, int nk, const double* probs, int n_probs, double* q_out,
+                                  uint64_t* M_out, int64_t* n_mass) {
+  const int64_t N = p.N;
   size_t fit = WQ_KEY_BYTES / ((size_t)N * 8);                         /* columns whose keys fit the chunk */
   fit = fit < 1 ? 1 : fit > WQ_CB ? WQ_CB : fit;
   const int ncc = (int)fit < nk ? (int)fit : nk;
@@ -339,7 +322,6 @@ int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t
   u64* parts = (u64*)(base + o_parts);
   u64* mass = (u64*)(base + o_mass);
   u64* keys = (u64*)(base + o_keys);
-  const SumPop p = sum_pop(ctx, bits, N, slot0, slot1, wns);
   const abz_model* dm = (const abz_model*)ctx->d_model;
 
   ABZ_HIP_CHECK(hipMemsetAsync(base, 0, o_parts, ctx->stream));        /* totals, results, states, histograms */
@@ -368,14 +350,7 @@ int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const uint32_t* bits, int64_t
   std::vector<u64> h(o_res / 8 + n_res);                                 /* totals and results are contiguous: one copy */
   ABZ_HIP_CHECK(hipMemcpyAsync(h.data(), base, o_res + n_res * 8, hipMemcpyDeviceToHost, ctx->stream));
   ABZ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (h[2] < 1) { abz_set_error("posterior_wquantiles: no particle has a positive weight that carries mass"); return -1; }
-  const unsigned __int128 Mfull = ((unsigned __int128)h[1] << 32) + (unsigned __int128)h[0];
-  if (Mfull >= ((unsigned __int128)1 << 63)) {
-    abz_set_error("posterior_wquantiles: the total mass reaches 2^63 -- the weights are not normalised (sum(Wns) must be about 1)");
-    return -1;
-  }
-  *M_out = (uint64_t)Mfull;
-  *n_mass = (int64_t)h[2];
+  if (sum_mass_verdict("posterior_wquantiles", h[0], h[1], h[2], M_out, n_mass)) return -1;
   memcpy(q_out, h.data() + o_res / 8, n_res * 8);
   return 0;
 }

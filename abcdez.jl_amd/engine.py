@@ -1325,6 +1325,12 @@ class PopulationEngine:
         w = self.wns
         return ((w[:, None] * th).sum(dim=0) / w.sum()).cpu().numpy()
 
+    def _live_population(self):
+        """``(bits, slot0, slot1, wns)`` of the live population: the leading arguments of the ``ops.posterior_*`` calls"""
+        if self.packed:
+            return self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns
+        return None, self.buf[self.cur][0], None, None
+
     def posterior_summary(self, cov: bool = True, corrected: bool = True, quantiles=(), wquantiles=(), hist=None):
         """Posterior summaries of the population where it lives (include/abcdez_spec.h, "posterior summaries"): a record with
         ``mean`` (d), ``cov`` (d x d; None without ``cov``), ``quantiles`` (len(quantiles) x d marginal type-7 quantiles over the
@@ -1356,10 +1362,7 @@ class PopulationEngine:
             return _summary.summary_reference(res["P"], res["Wns"] if self.packed else None, cov=cov, corrected=corrected,
                                               quantiles=probs, wquantiles=wprobs, hist=hist)
         self._stream()
-        if self.packed:
-            pop = (self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns)
-        else:
-            pop = (None, self.buf[self.cur][0], None, None)
+        pop = self._live_population()
         mean, S, W, Q, n_pos = self.ops.posterior_moments(*pop, self.N, want_second=cov)
         qs = np.empty((len(probs), self.spec.d))
         if probs:
@@ -1403,10 +1406,7 @@ class PopulationEngine:
                                         n_mass, n, draw)
         self._stream()
         self._sync_delta()
-        if self.packed:
-            pop = (self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns)
-        else:
-            pop = (None, self.buf[self.cur][0], None, None)
+        pop = self._live_population()
         idx, P, th, dl, st, M, n_mass = self.ops.posterior_sample(
             *pop, self.N, n, draw, delta=self.buf[self.cur][2], stamp=self.stamp[self.cur] if want_blobs else None, want_theta=want_blobs)
         send = [idx, P, dl]

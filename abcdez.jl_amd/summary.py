@@ -9,6 +9,7 @@ what an engine without the device call (the CPU test engine) computes from its d
 """
 from __future__ import annotations
 
+import bisect
 import math
 from builtins import range as builtins_range     # hist_reference has a `range` argument
 from types import SimpleNamespace
@@ -104,6 +105,26 @@ def weight_fix(w, n: int):
     return out
 
 
+def integer_masses(Wns, N: int, who: str = "summary"):
+    """(masses, M, n_mass): the integer masses of the N positions (Python integers; abz_weight_fix of the weights, or 2^b each
+    without weights), their total and the number of positions that count (mass >= 1).  Refuses like the library, under the
+    prefix ``who``: no mass at all, or a total that reaches 2^63."""
+    if Wns is None:
+        masses = [1 << stratum_bits(N)] * N
+    else:
+        w = np.asarray(Wns, dtype=np.float64)
+        if w.shape != (N,):
+            raise ValueError(f"{who}: one weight per particle expected")
+        masses = weight_fix(w, N)
+    n_mass = sum(1 for m in masses if m >= 1)
+    if n_mass < 1:
+        raise ValueError(f"{who}: no particle has a positive weight that carries mass")
+    M = sum(masses)
+    if M >= 1 << 63:
+        raise ValueError(f"{who}: the total mass reaches 2^63 -- the weights are not normalised")
+    return masses, M, n_mass
+
+
 def wquantile_column(values, masses, probs):
     """The weighted quantile of include/abcdez_spec.h ("posterior summaries", weighted quantiles) of ONE column, literally:
     ``values`` and ``masses`` (Python integers >= 1) of the counting positions; sort by (order key, mass), integer partial sums."""
@@ -117,7 +138,6 @@ def wquantile_column(values, masses, probs):
         s += x
         cum.append(s)                                   # S_1 .. S_n
     M = s
-    import bisect
     out = []
     for p in probs:
         span = M - m[0]
@@ -137,19 +157,14 @@ def wquantiles_reference(X, w, probs):
     """(wquantiles (len(probs) x d), M, n_mass) of the population X (N x d) with the weights w (None: every position has the
     mass 2^b); refuses like the library"""
     N, d = X.shape
-    masses = [1 << stratum_bits(N)] * N if w is None else weight_fix(w, N)
+    masses, M, n_mass = integer_masses(w, N)
     idx = [i for i in range(N) if masses[i] >= 1]
-    if not idx:
-        raise ValueError("summary: no particle has a positive weight that carries mass")
-    M = sum(masses)
-    if M >= 1 << 63:
-        raise ValueError("summary: the total mass reaches 2^63 -- the weights are not normalised")
     ml = [masses[i] for i in idx]
     out = np.empty((len(probs), d))
     with np.errstate(invalid="ignore", over="ignore"):
         for k in range(d):
             out[:, k] = wquantile_column(X[idx, k], ml, probs)
-    return out, M, len(idx)
+    return out, M, n_mass
 
 
 HIST_MAX_BINS, HIST_MAX_BINS2 = 4096, 128      # ABZ_HIST_MAX_BINS, ABZ_HIST_MAX_BINS2
@@ -267,13 +282,8 @@ def hist_reference(X, w, bins=64, range=None, columns=None, pairs=None, bins2=No
         X = X[:, None]
     N, d = X.shape
     cols, bins, rng_, pairs, bins2 = hist_options(dict(bins=bins, range=range, columns=columns, pairs=pairs, bins2=bins2), d)
-    masses = [1 << stratum_bits(N)] * N if w is None else weight_fix(w, N)
+    masses, M, n_mass = integer_masses(w, N)
     idx = [i for i in builtins_range(N) if masses[i] >= 1]
-    if not idx:
-        raise ValueError("summary: no particle has a positive weight that carries mass")
-    M = sum(masses)
-    if M >= 1 << 63:
-        raise ValueError("summary: the total mass reaches 2^63 -- the weights are not normalised")
     m = np.array([masses[i] for i in idx], dtype=np.uint64)        # every mass and every sum is below 2^63: exact in uint64
     nc = len(cols)
     lo_hi = np.empty((nc, 2))
@@ -306,7 +316,7 @@ def hist_reference(X, w, bins=64, range=None, columns=None, pairs=None, bins2=No
         inside = (bj < bins2) & (bk < bins2)
         np.add.at(mass2[q], bj[inside] * bins2 + bk[inside], m[inside])
         outside2[q] = m[~inside].sum(dtype=np.uint64)
-    return make_hist(cols, bins, lo_hi, cells1[:, :bins], cells1[:, bins:], pairs, bins2, mass2, outside2, M, len(idx))
+    return make_hist(cols, bins, lo_hi, cells1[:, :bins], cells1[:, bins:], pairs, bins2, mass2, outside2, M, n_mass)
 
 
 def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquantiles=(), hist=None):
@@ -395,37 +405,19 @@ def abz_rng(seed: int, idx: int, epoch: int, sub: int, purpose: int, rounds: int
     return (r[1] << 32) | r[0], (r[3] << 32) | r[2]
 
 
-def sample_masses(Wns, N: int):
-    """the integer masses of the N positions (Python integers): abz_weight_fix of the weights, or 2^b each without weights"""
-    if Wns is None:
-        return [1 << stratum_bits(N)] * N
-    w = np.asarray(Wns, dtype=np.float64)
-    if w.shape != (N,):
-        raise ValueError("sample: one weight per particle expected")
-    return weight_fix(w, N)
-
-
 def sample_reference(P, Wns, n, seed, draw: int = 0, rounds: int = 10):
     """The posterior sample of include/abcdez_spec.h ("posterior summaries", POSTERIOR SAMPLE), literally and in Python integers:
     ``(index, M, n_mass)`` with ``index`` (int64, n) the positions drawn for the strata 0 .. n - 1 -- ``P[index]`` is the sample.
     ``P``: the population (only its length is used; an int N is accepted), ``Wns``: the weights or None (abcdemc: unit masses),
     ``seed``: the run's 64-bit seed (``rng=``), ``rounds``: the Philox rounds of the stream (``abcdez_rng_rounds()``).  Refuses like
     the library."""
-    import bisect
-
     N = int(P) if isinstance(P, (int, np.integer)) else int(np.asarray(P).shape[0])
     n = int(n)
     if N < 1:
         raise ValueError("sample: the population is empty")
     if not 1 <= n <= SAMPLE_MAX_N:
         raise ValueError("sample: n must be in 1 .. 2^31 - 1")
-    masses = sample_masses(Wns, N)
-    n_mass = sum(1 for m in masses if m >= 1)
-    if n_mass < 1:
-        raise ValueError("sample: no particle has a positive weight that carries mass")
-    M = sum(masses)
-    if M >= 1 << 63:
-        raise ValueError("sample: the total mass reaches 2^63 -- the weights are not normalised")
+    masses, M, n_mass = integer_masses(Wns, N, "sample")
     if n > M:
         raise ValueError("sample: n exceeds the total mass M")
     q, r = divmod(M, n)
