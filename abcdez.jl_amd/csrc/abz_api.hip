@@ -108,10 +108,10 @@ extern "C" {
 
 /* 400: Philox4x32-10 again, abz_model.mv, group abort; 401: abcdemc's better particle by rejection;
  * 500: abcdez_comm_* and abcdez_smc_sweeps_sharded (RCCL behind the ABI), timing mode 3; 600: abcdez_comm_init_host (a host-supplied
- * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms; 650: abcdez_posterior_sample.  Hosts refuse a library older than the
+ * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms; 650: abcdez_posterior_sample; 660: abcdez_columns_moments / _wquantiles / _histograms.  Hosts refuse a library older than the
  * header they were written against (abcdez.jl_amd/_lib.py, julia/ABCdeZHIP.jl check_abi): a signature that grew an argument links
  * against an old binary without a diagnostic. */
-int abcdez_version(void) { return 650; }
+int abcdez_version(void) { return 660; }
 int abcdez_rng_rounds(void) { return ABZ_PHILOX_ROUNDS; }
 
 /* sizeof / offsetof of the two structs that cross the boundary, so that a host that mirrors them by hand (the Julia
@@ -669,7 +669,14 @@ int abcdez_blob_eval(abcdez_ctx* ctx, const double* theta, const uint64_t* stamp
   ABZ_REQUIRE(N >= 0 && N <= ABZ_MAX_N, "blob_eval: N out of range");
   ABZ_REQUIRE_LANES(ctx, N, "blob_eval");
   const uint32_t nbw = (uint32_t)(ctx->h_model.sim_id == ABZ_SIM_MVN ? ctx->h_model.ld : ctx->h_model.n_blob);
-  abz_population_written(ctx);         /* delta_out may be a distance array the library has state about */
+  /* delta_out may be a distance array the library has state about.  A select enqueued ahead read its own array (ahead.delta,
+   * ahead.N doubles): it stays valid unless delta_out overlaps that array -- a host that rebuilds blobs into a buffer of its own
+   * between two generations (result(), posterior_predictive) keeps the select it armed */
+  {
+    const abz_ahead keep = ctx->ahead;
+    abz_population_written(ctx);
+    if ((keep.armed || keep.valid) && keep.delta && (delta_out + N <= keep.delta || keep.delta + keep.N <= delta_out)) ctx->ahead = keep;
+  }
   return abz_launch_blob_eval(ctx, theta, stamp, N, blob, delta_out, nbw);
 }
 
@@ -1486,6 +1493,45 @@ static int posterior_probs(const char* call, const double* probs, int32_t n_prob
   return 0;
 }
 
+/* the arguments of the two histogram calls, checked alike: d columns to choose from, called `dim` in the messages (`things`:
+ * what the columns are) */
+static int histogram_args(const char* call, int32_t d, const char* dim_name, const char* things_name, const int32_t* cols, int32_t n_cols,
+                          int32_t bins, const double* range, const int32_t* pairs, int32_t n_pairs, int32_t bins2, const uint64_t* mass2,
+                          const uint64_t* outside2) {
+  const std::string who(call), dim(dim_name), things(things_name);
+  ABZ_REQUIRE(n_cols >= 1 && n_cols <= d, who + ": the columns must be 1 <= n_cols <= " + dim);
+  std::vector<char> asked((size_t)d, 0);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const int32_t k = cols ? cols[c] : c;
+    ABZ_REQUIRE(k >= 0 && k < d && (c == 0 || k > (cols ? cols[c - 1] : c - 1)),
+                who + ": the columns must be strictly increasing in 0 .. " + dim + " - 1");
+    asked[(size_t)k] = 1;
+  }
+  ABZ_REQUIRE(bins >= 1 && bins <= ABZ_HIST_MAX_BINS, who + ": bins must be in 1 .. 4096");
+  if (range)
+    for (int32_t c = 0; c < n_cols; ++c) {
+      const double lo = range[2 * c], hi = range[2 * c + 1], w = hi - lo;
+      ABZ_REQUIRE(lo < hi && lo >= -DBL_MAX && hi <= DBL_MAX && w <= DBL_MAX,
+                  who + ": a range must be finite with lo < hi and hi - lo finite");
+    }
+  ABZ_REQUIRE(n_pairs >= 0, who + ": n_pairs must not be negative");
+  if (n_pairs > 0) {
+    ABZ_REQUIRE(pairs && mass2 && outside2, who + ": pairs need the pair list, mass2 and outside2");
+    ABZ_REQUIRE(d >= 2, who + ": pairs need at least two " + things);
+    ABZ_REQUIRE(bins2 >= 1 && bins2 <= ABZ_HIST_MAX_BINS2, who + ": bins2 must be in 1 .. 128");
+    for (int32_t q = 0; q < n_pairs; ++q) {
+      const int32_t j = pairs[2 * q], k = pairs[2 * q + 1];
+      ABZ_REQUIRE(j >= 0 && k < d && j < k, who + ": a pair (j, k) needs two distinct columns with j < k");
+      ABZ_REQUIRE(asked[(size_t)j] && asked[(size_t)k], who + ": both columns of a pair must be among the requested columns");
+    }
+    std::vector<int64_t> seen((size_t)n_pairs);
+    for (int32_t q = 0; q < n_pairs; ++q) seen[(size_t)q] = (int64_t)pairs[2 * q] * d + pairs[2 * q + 1];
+    std::sort(seen.begin(), seen.end());
+    ABZ_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), who + ": a pair must not be listed twice");
+  }
+  return 0;
+}
+
 /* Posterior summaries (csrc/abz_summary.hip).  Neither call touches a select enqueued ahead or the chain of asynchronous abcdemc
  * generations: they only read the population. */
 int abcdez_posterior_moments(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
@@ -1531,37 +1577,9 @@ int abcdez_posterior_histograms(abcdez_ctx* ctx, const uint32_t* bits, int64_t N
                                 uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass) {
   SumPop p;
   if (posterior_pop("posterior_histograms", ctx, bits, N, slot0, slot1, wns, lo_hi && mass1 && tallies1 && M && n_mass, &p)) return -1;
-  const int32_t d = (int32_t)ctx->h_model.d;
-  ABZ_REQUIRE(n_cols >= 1 && n_cols <= d, "posterior_histograms: the columns must be 1 <= n_cols <= length(prior)");
-  std::vector<char> asked((size_t)d, 0);
-  for (int32_t c = 0; c < n_cols; ++c) {
-    const int32_t k = cols ? cols[c] : c;
-    ABZ_REQUIRE(k >= 0 && k < d && (c == 0 || k > (cols ? cols[c - 1] : c - 1)),
-                "posterior_histograms: the columns must be strictly increasing in 0 .. length(prior) - 1");
-    asked[(size_t)k] = 1;
-  }
-  ABZ_REQUIRE(bins >= 1 && bins <= ABZ_HIST_MAX_BINS, "posterior_histograms: bins must be in 1 .. 4096");
-  if (range)
-    for (int32_t c = 0; c < n_cols; ++c) {
-      const double lo = range[2 * c], hi = range[2 * c + 1], w = hi - lo;
-      ABZ_REQUIRE(lo < hi && lo >= -DBL_MAX && hi <= DBL_MAX && w <= DBL_MAX,
-                  "posterior_histograms: a range must be finite with lo < hi and hi - lo finite");
-    }
-  ABZ_REQUIRE(n_pairs >= 0, "posterior_histograms: n_pairs must not be negative");
-  if (n_pairs > 0) {
-    ABZ_REQUIRE(pairs && mass2 && outside2, "posterior_histograms: pairs need the pair list, mass2 and outside2");
-    ABZ_REQUIRE(d >= 2, "posterior_histograms: pairs need at least two parameters");
-    ABZ_REQUIRE(bins2 >= 1 && bins2 <= ABZ_HIST_MAX_BINS2, "posterior_histograms: bins2 must be in 1 .. 128");
-    for (int32_t q = 0; q < n_pairs; ++q) {
-      const int32_t j = pairs[2 * q], k = pairs[2 * q + 1];
-      ABZ_REQUIRE(j >= 0 && k < d && j < k, "posterior_histograms: a pair (j, k) needs two distinct columns with j < k");
-      ABZ_REQUIRE(asked[(size_t)j] && asked[(size_t)k], "posterior_histograms: both columns of a pair must be among the requested columns");
-    }
-    std::vector<int64_t> seen((size_t)n_pairs);
-    for (int32_t q = 0; q < n_pairs; ++q) seen[(size_t)q] = (int64_t)pairs[2 * q] * d + pairs[2 * q + 1];
-    std::sort(seen.begin(), seen.end());
-    ABZ_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "posterior_histograms: a pair must not be listed twice");
-  }
+  if (histogram_args("posterior_histograms", (int32_t)ctx->h_model.d, "length(prior)", "parameters", cols, n_cols, bins, range, pairs,
+                     n_pairs, bins2, mass2, outside2))
+    return -1;
   return abz_posterior_histograms_impl(ctx, p, cols, n_cols, bins, range, pairs, n_pairs, bins2, lo_hi, mass1, tallies1, mass2, outside2,
                                        M, n_mass);
 }
@@ -1578,6 +1596,49 @@ int abcdez_posterior_sample(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, co
   ABZ_REQUIRE((delta != nullptr) == (delta_out != nullptr), "posterior_sample: delta_out is given iff delta is");
   ABZ_REQUIRE((stamp != nullptr) == (stamp_out != nullptr), "posterior_sample: stamp_out is given iff stamp is");
   return abz_posterior_sample_impl(ctx, p, n, draw, delta, stamp, idx_out, P_out, theta_out, delta_out, stamp_out, M, n_mass);
+}
+
+/* Column summaries (csrc/abz_columns.hip): the three summaries above of a dense per-particle matrix X[N][ldx] -- the simulated
+ * data behind the particles, for the posterior predictive check -- instead of the parameter rows.  Like their neighbours they only
+ * read, and their scratch is the summaries' buffer. */
+static int columns_view(const char* call, abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,
+                        bool rest, ColView* v) {
+  const std::string who(call);
+  ABZ_REQUIRE(ctx && X && rest, who + ": null argument");
+  ABZ_REQUIRE(N >= 1 && N <= ABZ_MAX_N, who + ": N out of range");
+  ABZ_REQUIRE(m >= 1 && m <= ABZ_COLS_MAX_M, who + ": m must be in 1 .. 256");
+  ABZ_REQUIRE(ldx >= m, who + ": ldx must be at least m");
+  v->X = X; v->wns = wns; v->N = N; v->ldx = ldx; v->m = m;
+  return 0;
+}
+
+int abcdez_columns_moments(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,
+                           int32_t want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos) {
+  ColView v;
+  if (columns_view("columns_moments", ctx, X, ldx, m, wns, N, mean && W && Q && n_pos, &v)) return -1;
+  ABZ_REQUIRE(!want_second || S, "columns_moments: want_second without an array for S");
+  return abz_columns_moments_impl(ctx, v, want_second != 0, mean, S, W, Q, n_pos);
+}
+
+int abcdez_columns_wquantiles(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N, int32_t k0,
+                              int32_t nk, const double* probs, int32_t n_probs, double* q_out, uint64_t* M, int64_t* n_mass) {
+  ColView v;
+  if (columns_view("columns_wquantiles", ctx, X, ldx, m, wns, N, probs && q_out && M && n_mass, &v)) return -1;
+  ABZ_REQUIRE(nk >= 1 && k0 >= 0 && (int64_t)k0 + (int64_t)nk <= (int64_t)m,
+              "columns_wquantiles: the columns must be 0 <= k0, nk >= 1, k0 + nk <= m");
+  if (posterior_probs("columns_wquantiles", probs, n_probs)) return -1;
+  return abz_columns_wquantiles_impl(ctx, v, k0, nk, probs, n_probs, q_out, M, n_mass);
+}
+
+int abcdez_columns_histograms(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,
+                              const int32_t* cols, int32_t n_cols, int32_t bins, const double* range, const int32_t* pairs,
+                              int32_t n_pairs, int32_t bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1, uint64_t* mass2,
+                              uint64_t* outside2, uint64_t* M, int64_t* n_mass) {
+  ColView v;
+  if (columns_view("columns_histograms", ctx, X, ldx, m, wns, N, lo_hi && mass1 && tallies1 && M && n_mass, &v)) return -1;
+  if (histogram_args("columns_histograms", m, "m", "columns", cols, n_cols, bins, range, pairs, n_pairs, bins2, mass2, outside2)) return -1;
+  return abz_columns_histograms_impl(ctx, v, cols, n_cols, bins, range, pairs, n_pairs, bins2, lo_hi, mass1, tallies1, mass2, outside2, M,
+                                     n_mass);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

@@ -30,7 +30,7 @@
 #define HB_K 16               /* pairs (columns k) per batch */
 #define H1_CELLS 5120         /* 40 KB: 1-D cells per workgroup */
 #define H2_CELLS 8192         /* 64 KB: 2-D cells per workgroup */
-#define H_RC 8                /* range: columns per launch (64 bytes of a row; 16 spill scalar registers) */
+/* H_RC (abz_summary.h): range, columns per launch (64 bytes of a row; 16 spill scalar registers) */
 #define H_VEC 4               /* positions per thread and tile in the two histogram passes */
 #define H_TILE (ABZ_BLOCK * H_VEC)
 #define H_PAD 16              /* the column stride is a multiple of this: 4 x u16 and 4 x u8 loads stay aligned */
@@ -42,7 +42,7 @@
 
 typedef unsigned long long u64;
 
-struct HistCol { double lo, hi, scale, scale2; int32_t col, pad; };
+/* HistCol (abz_summary.h): a requested column, its range and the two scales */
 struct HistBatch { int32_t cj, n, r0, r1; int32_t ck[HB_K]; int32_t pair[HB_K]; };
 
 /* ---- range: krange[2 c + {0, 1}] = (smallest, largest) order key of requested column c over the counting positions, for the
@@ -245,11 +245,9 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_pair_kernel(const u64* __restr
 }
 
 /* ================================================================ host side */
-int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_t* cols, int nc, int bins, const double* range,
-                                  const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
-                                  uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
-  const int64_t N = p.N;
-  const int d = p.d;
+int abz_histograms_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const SumHistGather& src, const int32_t* cols, int nc,
+                         int bins, const double* range, const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1,
+                         uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
   /* the blob the host uploads: [ columns | key ranges | batches ] */
   std::vector<int> pos((size_t)d, -1);
   std::vector<HistCol> hc((size_t)nc);
@@ -312,7 +310,6 @@ int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_
   u64* mass = (u64*)(base + o_mass);
   uint16_t* idx1 = (uint16_t*)(base + o_idx1);
   uint8_t* idx2 = n_pairs > 0 ? (uint8_t*)(base + o_idx2) : nullptr;
-  const abz_model* dm = (const abz_model*)ctx->d_model;
 
   ABZ_HIP_CHECK(hipMemsetAsync(base, 0, o_blob, ctx->stream));
   ABZ_HIP_CHECK(hipMemcpyAsync(base + o_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -320,16 +317,14 @@ int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_
   if (!range) {
     const int nb = (int)(nb64 < H_RANGE_BLOCKS ? nb64 : H_RANGE_BLOCKS);
     for (int c0 = 0; c0 < nc; c0 += H_RC)
-      hipLaunchKernelGGL(hist_range_kernel, dim3((unsigned)nb), dim3(ABZ_BLOCK), 0, ctx->stream, dm, p, (const HistCol*)dcols, c0,
-                         nc - c0 < H_RC ? nc - c0 : H_RC, krange);
+      src.range(ctx->stream, (unsigned)nb, (const HistCol*)dcols, c0, nc - c0 < H_RC ? nc - c0 : H_RC, krange);
   }
   hipLaunchKernelGGL(hist_setup_kernel, dim3(1), dim3(ABZ_BLOCK), 0, ctx->stream, dcols, nc, range ? 0 : 1, (const u64*)krange, bins,
                      bins2, lohi, hdr);
   {
     const int64_t nbl = (Nld + ABZ_BLOCK - 1) / ABZ_BLOCK;
     const int nb = (int)(nbl < H_BIN_BLOCKS ? nbl : H_BIN_BLOCKS);
-    hipLaunchKernelGGL(hist_bin_kernel, dim3((unsigned)nb), dim3(ABZ_BLOCK), 0, ctx->stream, dm, p, (const HistCol*)dcols, nc, bins,
-                       bins2, Nld, mass, idx1, idx2, hdr);
+    src.bin(ctx->stream, (unsigned)nb, (const HistCol*)dcols, nc, bins, bins2, Nld, mass, idx1, idx2, hdr);
   }
   const int64_t tiles = (Nld + H_TILE - 1) / H_TILE;
   {
@@ -356,10 +351,10 @@ int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_
   ABZ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   uint64_t Mv = 0;
   int64_t nm = 0;
-  if (sum_mass_verdict("posterior_histograms", h[0], h[1], h[2], &Mv, &nm)) return -1;
+  if (sum_mass_verdict(call, h[0], h[1], h[2], &Mv, &nm)) return -1;
   if (h[3]) {
     const int c = nc - (int)h[3];
-    abz_set_error("posterior_histograms: the automatic range of column " + std::to_string(hc[c].col) +
+    abz_set_error(std::string(call) + ": the automatic range of column " + std::to_string(hc[c].col) +
                   " is not usable (a NaN or an infinity among the counting rows, or hi - lo not finite): pass a range");
     return -1;
   }
@@ -378,4 +373,24 @@ int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_
     outside2[q] = Mv - in;
   }
   return 0;
+}
+
+struct PopHistGather : SumHistGather {              /* the population's parameter rows, push_p-cast */
+  const abz_model* M;
+  SumPop p;
+  void range(hipStream_t s, unsigned nb, const HistCol* cols, int c0, int ncols, u64* krange) const override {
+    hipLaunchKernelGGL(hist_range_kernel, dim3(nb), dim3(ABZ_BLOCK), 0, s, M, p, cols, c0, ncols, krange);
+  }
+  void bin(hipStream_t s, unsigned nb, const HistCol* cols, int nc, int bins, int bins2, int64_t Nld, u64* mass, uint16_t* idx1,
+           uint8_t* idx2, u64* tot) const override {
+    hipLaunchKernelGGL(hist_bin_kernel, dim3(nb), dim3(ABZ_BLOCK), 0, s, M, p, cols, nc, bins, bins2, Nld, mass, idx1, idx2, tot);
+  }
+};
+int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_t* cols, int nc, int bins, const double* range,
+                                  const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
+                                  uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
+  PopHistGather g;
+  g.M = (const abz_model*)ctx->d_model; g.p = p;
+  return abz_histograms_drive(ctx, "posterior_histograms", p.N, p.d, g, cols, nc, bins, range, pairs, n_pairs, bins2, lo_hi, mass1,
+                              tallies1, mass2, outside2, M_out, n_mass);
 }

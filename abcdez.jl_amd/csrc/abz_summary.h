@@ -1,6 +1,7 @@
-/* abz_summary.h -- what the posterior calls share (abz_summary.hip, abz_wquantile.hip, abz_hist.hip, abz_sample.hip and their
- * entry points in abz_api.hip): the view of a population, the current row and the integer mass of a position, the tally of the
- * masses and its verdict, and the calls' buffer in the context. */
+/* abz_summary.h -- what the posterior calls share (abz_summary.hip, abz_wquantile.hip, abz_hist.hip, abz_sample.hip, abz_columns.hip
+ * and their entry points in abz_api.hip): the view of a population, the current row and the integer mass of a position, the tally
+ * of the masses and its verdict, the calls' buffer in the context, and the drivers of the passes that do not depend on where the
+ * values come from (the population's parameter rows, or any dense per-particle matrix: abz_columns.hip). */
 #pragma once
 #include "abz_ctx.h"
 #include "abz_device.h"
@@ -20,6 +21,22 @@ static inline SumPop sum_pop(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, c
   p.ld = ctx->h_model.ld; p.d = ctx->h_model.d;
   return p;
 }
+
+/* a dense per-particle matrix X[N][ldx] (its first m columns are the values) under the population's weights: what
+ * abz_columns.hip summarises -- the simulated data behind the particles (posterior predictive), taken as they are (no push_p) */
+struct ColView {
+  const double* X;
+  const double* wns;        /* NULL: unit weights */
+  int64_t N;
+  int ldx, m;
+};
+
+#define ABZ_COLS_MAX_M 256  /* columns of a ColView at most (the second-moment pass keeps 4 x m x 4 sums in LDS) */
+#define WQ_CB 16            /* weighted quantiles: columns per chunk, 128 bytes of a row */
+#define H_RC 8              /* histograms, range: columns per launch (64 bytes of a row; 16 spill scalar registers) */
+
+/* histograms: a requested column, its range and the two scales (abz_hist.hip) */
+struct HistCol { double lo, hi, scale, scale2; int32_t col, pad; };
 
 /* ---- device side */
 /* the current row of position i: the slot its bit names */
@@ -68,6 +85,30 @@ int sum_mass_refuse(const char* call, bool too_heavy);
 int sum_mass_verdict(const char* call, unsigned long long lo, unsigned long long hi, unsigned long long cnt, uint64_t* M_out,
                      int64_t* n_mass);
 
+/* ---- the launches that read the values.  Every other pass of the three calls (tree finish, radix passes, LDS histograms) works
+ * on what these leave in the buffer, so a call over another source of values brings its own gathers and shares the driver. */
+struct SumMomentsGather {   /* sum_first_kernel / sum_second_kernel and their twins: one block per tile of ABZ_TILE positions */
+  virtual void first(hipStream_t s, unsigned nt, double* parts, unsigned long long* n_pos) const = 0;
+  virtual void second(hipStream_t s, unsigned nt, const double* mean, double* parts) const = 0;
+};
+struct SumWqGather {        /* wq_gather_kernel and its twin: the columns c0 .. c0 + ncols - 1 of the call's range */
+  virtual void gather(hipStream_t s, unsigned nb, int c0, int ncols, unsigned long long* keys, unsigned long long* mass,
+                      int first_chunk, unsigned long long* parts, unsigned long long* tot) const = 0;
+};
+struct SumHistGather {      /* hist_range_kernel / hist_bin_kernel and their twins */
+  virtual void range(hipStream_t s, unsigned nb, const HistCol* cols, int c0, int ncols, unsigned long long* krange) const = 0;
+  virtual void bin(hipStream_t s, unsigned nb, const HistCol* cols, int nc, int bins, int bins2, int64_t Nld,
+                   unsigned long long* mass, uint16_t* idx1, uint8_t* idx2, unsigned long long* tot) const = 0;
+};
+/* the drivers: `call` names the entry point in the refusals, d = the number of columns the source has */
+int abz_moments_drive(abcdez_ctx*, const char* call, int64_t N, int d, const SumMomentsGather&, int want_second, double* mean,
+                      double* S, double* W, double* Q, int64_t* n_pos);
+int abz_wquantiles_drive(abcdez_ctx*, const char* call, int64_t N, int nk, const SumWqGather&, const double* probs, int n_probs,
+                         double* q_out, uint64_t* M, int64_t* n_mass);
+int abz_histograms_drive(abcdez_ctx*, const char* call, int64_t N, int d, const SumHistGather&, const int32_t* cols, int n_cols,
+                         int bins, const double* range, const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1,
+                         uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass);
+
 int abz_posterior_moments_impl(abcdez_ctx*, const SumPop&, int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
 int abz_posterior_quantiles_impl(abcdez_ctx*, const SumPop&, int k, const double* probs, int n_probs, double* q_out);
 int abz_posterior_wquantiles_impl(abcdez_ctx*, const SumPop&, int k0, int nk, const double* probs, int n_probs, double* q_out, uint64_t* M,
@@ -78,3 +119,10 @@ int abz_posterior_histograms_impl(abcdez_ctx*, const SumPop&, const int32_t* col
 int abz_posterior_sample_impl(abcdez_ctx*, const SumPop&, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
                               uint32_t* idx_out, double* P_out, double* theta_out, double* delta_out, uint64_t* stamp_out, uint64_t* M,
                               int64_t* n_mass);
+/* abz_columns.hip */
+int abz_columns_moments_impl(abcdez_ctx*, const ColView&, int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
+int abz_columns_wquantiles_impl(abcdez_ctx*, const ColView&, int k0, int nk, const double* probs, int n_probs, double* q_out, uint64_t* M,
+                                int64_t* n_mass);
+int abz_columns_histograms_impl(abcdez_ctx*, const ColView&, const int32_t* cols, int n_cols, int bins, const double* range,
+                                const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
+                                uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass);

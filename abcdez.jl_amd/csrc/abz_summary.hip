@@ -250,10 +250,8 @@ int sum_mass_verdict(const char* call, unsigned long long lo, unsigned long long
   return 0;
 }
 
-int abz_posterior_moments_impl(abcdez_ctx* ctx, const SumPop& p, int want_second, double* mean, double* S, double* W, double* Q,
-                               int64_t* n_pos) {
-  const int64_t N = p.N;
-  const int d = p.d;
+int abz_moments_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const SumMomentsGather& src, int want_second, double* mean,
+                      double* S, double* W, double* Q, int64_t* n_pos) {
   const size_t nt = (size_t)((N + ABZ_TILE - 1) / ABZ_TILE);
   const size_t npairs = (size_t)d * (size_t)(d + 1) / 2;
   const size_t ntrees = want_second && npairs > (size_t)d + 2 ? npairs : (size_t)d + 2;
@@ -268,7 +266,7 @@ int abz_posterior_moments_impl(abcdez_ctx* ctx, const SumPop& p, int want_second
   double* parts = (double*)(base + o_parts);
 
   ABZ_HIP_CHECK(hipMemsetAsync(d_npos, 0, 8, ctx->stream));
-  hipLaunchKernelGGL(sum_first_kernel, dim3((unsigned)nt), dim3(ABZ_BLOCK), 0, ctx->stream, (const abz_model*)ctx->d_model, p, parts, d_npos);
+  src.first(ctx->stream, (unsigned)nt, parts, d_npos);
   SumFinishArgs f{parts, (int64_t)nt, res1, d, d};
   hipLaunchKernelGGL(sum_finish_kernel, dim3((unsigned)(d + 2)), dim3(ABZ_BLOCK), 0, ctx->stream, f);
   ABZ_HIP_CHECK(hipGetLastError());
@@ -277,13 +275,12 @@ int abz_posterior_moments_impl(abcdez_ctx* ctx, const SumPop& p, int want_second
   ABZ_HIP_CHECK(hipMemcpyAsync(h1.data(), res1, ((size_t)d + 2) * 8, hipMemcpyDeviceToHost, ctx->stream));
   ABZ_HIP_CHECK(hipMemcpyAsync(&h_npos, d_npos, 8, hipMemcpyDeviceToHost, ctx->stream));
   ABZ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (h_npos < 1) { abz_set_error("posterior_moments: no particle has a positive weight"); return -1; }
+  if (h_npos < 1) { abz_set_error(std::string(call) + ": no particle has a positive weight"); return -1; }
   memcpy(mean, h1.data(), (size_t)d * 8);
   *W = h1[d]; *Q = h1[d + 1]; *n_pos = (int64_t)h_npos;
   if (!want_second) return 0;
 
-  hipLaunchKernelGGL(sum_second_kernel, dim3((unsigned)nt), dim3(ABZ_BLOCK), 0, ctx->stream, (const abz_model*)ctx->d_model, p,
-                     (const double*)res1, parts);
+  src.second(ctx->stream, (unsigned)nt, (const double*)res1, parts);
   SumFinishArgs g{parts, (int64_t)nt, res2, 0, 0};
   hipLaunchKernelGGL(sum_finish_kernel, dim3((unsigned)npairs), dim3(ABZ_BLOCK), 0, ctx->stream, g);
   ABZ_HIP_CHECK(hipGetLastError());
@@ -294,6 +291,23 @@ int abz_posterior_moments_impl(abcdez_ctx* ctx, const SumPop& p, int want_second
   for (int j = 0; j < d; ++j)
     for (int k = j; k < d; ++k, ++pair) S[(size_t)j * d + k] = S[(size_t)k * d + j] = h2[pair];
   return 0;
+}
+
+struct PopMomentsGather : SumMomentsGather {       /* the population's parameter rows, push_p-cast */
+  const abz_model* M;
+  SumPop p;
+  void first(hipStream_t s, unsigned nt, double* parts, unsigned long long* n_pos) const override {
+    hipLaunchKernelGGL(sum_first_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, s, M, p, parts, n_pos);
+  }
+  void second(hipStream_t s, unsigned nt, const double* mean, double* parts) const override {
+    hipLaunchKernelGGL(sum_second_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, s, M, p, mean, parts);
+  }
+};
+int abz_posterior_moments_impl(abcdez_ctx* ctx, const SumPop& p, int want_second, double* mean, double* S, double* W, double* Q,
+                               int64_t* n_pos) {
+  PopMomentsGather g;
+  g.M = (const abz_model*)ctx->d_model; g.p = p;
+  return abz_moments_drive(ctx, "posterior_moments", p.N, p.d, g, want_second, mean, S, W, Q, n_pos);
 }
 
 int abz_posterior_quantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k, const double* probs, int n_probs, double* q_out) {

@@ -26,7 +26,7 @@
 #include "abz_summary.h"
 
 #define WQ_PB 16            /* probabilities per batch: one 256-bin histogram each, 32 KB of LDS */
-#define WQ_CB 16            /* columns per chunk: 128 bytes of a row */
+/* WQ_CB (abz_summary.h): columns per chunk, 128 bytes of a row */
 #define WQ_ITEMS 8          /* positions per thread and tile in the passes */
 #define WQ_TILE (ABZ_BLOCK * WQ_ITEMS)
 #define WQ_MAX_BLOCKS 2048  /* gather: blocks (and partials per column) */
@@ -297,9 +297,8 @@ __global__ void wq_final_kernel(const WqState* __restrict__ st, int np, double* 
 }
 
 /* ================================================================ host side */
-int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k0, int nk, const double* probs, int n_probs, double* q_out,
-                                  uint64_t* M_out, int64_t* n_mass) {
-  const int64_t N = p.N;
+int abz_wquantiles_drive(abcdez_ctx* ctx, const char* call, int64_t N, int nk, const SumWqGather& src, const double* probs, int n_probs,
+                         double* q_out, uint64_t* M_out, int64_t* n_mass) {
   size_t fit = WQ_KEY_BYTES / ((size_t)N * 8);                         /* columns whose keys fit the chunk */
   fit = fit < 1 ? 1 : fit > WQ_CB ? WQ_CB : fit;
   const int ncc = (int)fit < nk ? (int)fit : nk;
@@ -322,13 +321,11 @@ int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k0, int 
   u64* parts = (u64*)(base + o_parts);
   u64* mass = (u64*)(base + o_mass);
   u64* keys = (u64*)(base + o_keys);
-  const abz_model* dm = (const abz_model*)ctx->d_model;
 
   ABZ_HIP_CHECK(hipMemsetAsync(base, 0, o_parts, ctx->stream));        /* totals, results, states, histograms */
   for (int c0 = 0; c0 < nk; c0 += ncc) {
     const int nc = nk - c0 < ncc ? nk - c0 : ncc;
-    hipLaunchKernelGGL(wq_gather_kernel, dim3((unsigned)nb), dim3(ABZ_BLOCK), 0, ctx->stream, dm, p, k0 + c0, nc, keys, mass,
-                       c0 == 0 ? 1 : 0, parts, tot);
+    src.gather(ctx->stream, (unsigned)nb, c0, nc, keys, mass, c0 == 0 ? 1 : 0, parts, tot);
     for (int q0 = 0; q0 < n_probs; q0 += WQ_PB) {
       WqProbs pr{};
       pr.n = n_probs - q0 < WQ_PB ? n_probs - q0 : WQ_PB;
@@ -350,7 +347,22 @@ int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k0, int 
   std::vector<u64> h(o_res / 8 + n_res);                                 /* totals and results are contiguous: one copy */
   ABZ_HIP_CHECK(hipMemcpyAsync(h.data(), base, o_res + n_res * 8, hipMemcpyDeviceToHost, ctx->stream));
   ABZ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (sum_mass_verdict("posterior_wquantiles", h[0], h[1], h[2], M_out, n_mass)) return -1;
+  if (sum_mass_verdict(call, h[0], h[1], h[2], M_out, n_mass)) return -1;
   memcpy(q_out, h.data() + o_res / 8, n_res * 8);
   return 0;
+}
+
+struct PopWqGather : SumWqGather {                  /* the population's parameter rows from column k0 on, push_p-cast */
+  const abz_model* M;
+  SumPop p;
+  int k0;
+  void gather(hipStream_t s, unsigned nb, int c0, int ncols, u64* keys, u64* mass, int first_chunk, u64* parts, u64* tot) const override {
+    hipLaunchKernelGGL(wq_gather_kernel, dim3(nb), dim3(ABZ_BLOCK), 0, s, M, p, k0 + c0, ncols, keys, mass, first_chunk, parts, tot);
+  }
+};
+int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k0, int nk, const double* probs, int n_probs, double* q_out,
+                                  uint64_t* M_out, int64_t* n_mass) {
+  PopWqGather g;
+  g.M = (const abz_model*)ctx->d_model; g.p = p; g.k0 = k0;
+  return abz_wquantiles_drive(ctx, "posterior_wquantiles", p.N, nk, g, probs, n_probs, q_out, M_out, n_mass);
 }

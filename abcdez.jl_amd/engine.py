@@ -542,6 +542,67 @@ class HipOps:
                                 _ptr(stamp), _ptr(idx), _ptr(P), _ptr(theta), _ptr(dl), _ptr(st), C.byref(M), C.byref(n_mass)))
         return idx, P, theta, dl, st, M.value, n_mass.value
 
+    # ---- column summaries: the same three summaries of any dense per-particle matrix (include/abcdez_hip.h, R2) ----
+    @staticmethod
+    def _columns_view(X, m):
+        """(ldx, m) of a device matrix X[N][ldx] whose first m columns (default: all) are the values"""
+        if X.dim() != 2 or X.dtype != torch.float64 or not X.is_contiguous():
+            raise ValueError("columns: X must be a contiguous float64 matrix N x ldx")
+        return int(X.shape[1]), int(X.shape[1] if m is None else m)
+
+    def columns_moments(self, X, wns, m=None, want_second=True):
+        """(mean[m], S[m, m] or None, W, Q, n_pos) of the first m columns of the device matrix X[N][ldx] under the weights wns
+        (None: unit weights), abcdez_columns_moments"""
+        ldx, m = self._columns_view(X, m)
+        mm = max(m, 1)
+        mean = np.empty(mm, dtype=np.float64)
+        S = np.empty((mm, mm), dtype=np.float64) if want_second else None
+        W, Q, n_pos = C.c_double(), C.c_double(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn("abcdez_columns_moments", 660)(
+            self.ctx, _ptr(X), ldx, m, _ptr(wns), int(X.shape[0]), 1 if want_second else 0, mean.ctypes.data,
+            S.ctypes.data if want_second else None, C.byref(W), C.byref(Q), C.byref(n_pos)))
+        return mean, S, W.value, Q.value, n_pos.value
+
+    def columns_wquantiles(self, X, wns, probs, m=None, k0=0, nk=None):
+        """(q[nk, len(probs)], M, n_mass): weighted quantiles at ``probs`` of the columns k0 .. k0 + nk - 1 (default: all from k0
+        up to m) of X over the integer masses of the resampler, one library call and one read-back (abcdez_columns_wquantiles)"""
+        ldx, m = self._columns_view(X, m)
+        nk = m - int(k0) if nk is None else int(nk)
+        p = np.ascontiguousarray(probs, dtype=np.float64)
+        q = np.empty((max(nk, 0), p.size), dtype=np.float64)
+        M, n_mass = C.c_uint64(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn("abcdez_columns_wquantiles", 660)(
+            self.ctx, _ptr(X), ldx, m, _ptr(wns), int(X.shape[0]), int(k0), nk, p.ctypes.data, int(p.size), q.ctypes.data,
+            C.byref(M), C.byref(n_mass)))
+        return q, M.value, n_mass.value
+
+    def columns_histograms(self, X, wns, m=None, columns=None, bins=64, range=None, pairs=(), bins2=None):
+        """(lo_hi[n_cols, 2], mass1[n_cols, bins], tallies1[n_cols, 3], mass2[n_pairs, bins2, bins2], outside2[n_pairs], M, n_mass):
+        marginal and pairwise histograms of columns of X over the integer masses of the resampler, one library call
+        (abcdez_columns_histograms); the arguments are those of :meth:`posterior_histograms` with column indices in 0 .. m - 1"""
+        ldx, m = self._columns_view(X, m)
+        cols = np.arange(max(m, 0), dtype=np.int32) if columns is None else np.ascontiguousarray(columns, dtype=np.int32).reshape(-1)
+        nc = int(cols.size)
+        bins, bins2 = int(bins), int(bins if bins2 is None else bins2)
+        rg = None if range is None else np.ascontiguousarray(range, dtype=np.float64).reshape(-1)
+        if rg is not None and rg.size != 2 * nc:
+            raise ValueError("columns_histograms: range must hold (lo, hi) per requested column")
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        npairs = int(pr.shape[0])
+        lo_hi = np.empty((nc, 2), dtype=np.float64)
+        mass1 = np.zeros((nc, max(bins, 0)), dtype=np.uint64)
+        tallies1 = np.zeros((nc, 3), dtype=np.uint64)
+        b2 = max(bins2, 0) if npairs else 0
+        mass2 = np.zeros((npairs, b2, b2), dtype=np.uint64)
+        outside2 = np.zeros(npairs, dtype=np.uint64)
+        M, n_mass = C.c_uint64(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn("abcdez_columns_histograms", 660)(
+            self.ctx, _ptr(X), ldx, m, _ptr(wns), int(X.shape[0]), cols.ctypes.data, nc, bins,
+            None if rg is None else rg.ctypes.data, pr.ctypes.data if npairs else None, npairs, bins2, lo_hi.ctypes.data,
+            mass1.ctypes.data, tallies1.ctypes.data, mass2.ctypes.data if npairs else None, outside2.ctypes.data if npairs else None,
+            C.byref(M), C.byref(n_mass)))
+        return lo_hi, mass1, tallies1, mass2, outside2, M.value, n_mass.value
+
     def set_stamps(self, cur, nxt):
         _lib.check(self.lib, self.lib.abcdez_ctx_set_stamps(self.ctx, _ptr(cur), _ptr(nxt)))
 
@@ -1425,6 +1486,58 @@ class PopulationEngine:
         if want_blobs:
             bl = got[3][:, 0] if got[3].shape[1] == 1 else got[3]
         return _summary.make_sample(Ph, got[0].astype(np.int64), got[2], bl, M, n_mass, n, draw)
+
+    def posterior_predictive(self, cov: bool = False, corrected: bool = True, wquantiles=(), hist=None):
+        """Posterior predictive summaries: the summaries of :meth:`posterior_summary` for the SIMULATED DATA behind the particles
+        (the reference's blobs, docs/src/index.md:298-324) instead of the parameters -- weighted mean, covariance and credible
+        bands of the accepted simulations per observation, what a posterior predictive check draws over the data.  Returns the
+        record of :func:`abcdez_amd.summary.make_summary` over the columns 0 .. n_blob - 1: ``mean`` (n_blob), ``cov`` / ``S``
+        (n_blob x n_blob; None without ``cov``), ``W``, ``Q``, ``ess``, ``n_pos``, ``wquantiles`` (len(wquantiles) x n_blob) with
+        ``wprobs``, ``M``, ``n_mass``, and ``hist`` (the options of :meth:`posterior_summary`, column indices in 0 .. n_blob - 1);
+        ``quantiles`` is empty (the weighted ones serve every kernel).  abcdemc has no weights: every particle counts once.
+
+        On the HIP engine the blobs of all N positions are rebuilt on the device from the stamps of the current generation, exactly
+        as :meth:`result` does it (the re-run's distance is checked bit for bit against the stored one), summarised there under the
+        population's weights (csrc/abz_columns.hip; bit for bit :func:`abcdez_amd.summary.predictive_reference` of the downloaded
+        ``blobs`` and ``Wns``) and freed: only the summary travels to the host.  It needs N x blob_width x 8 bytes of device memory
+        for the matrix while it runs, and changes nothing a continued run depends on.  Engines without the device call compute the
+        restatement on ``result()["blobs"]``.  A simulator without blobs is refused."""
+        from . import summary as _summary
+
+        wprobs = tuple(float(p) for p in wquantiles)
+        if any(not 0.0 <= p <= 1.0 for p in wprobs):
+            raise ValueError("predictive: p must be in [0, 1]")
+        if not self.blob_on:
+            raise ValueError(_summary.PREDICTIVE_NEEDS_BLOBS)
+        nb = self.spec.n_blob
+        if hist is not None and hist is not False:
+            hist_opts = _summary.hist_options(hist, nb)
+        if not hasattr(self.ops, "columns_moments"):
+            res = self.result()
+            return _summary.predictive_reference(res["blobs"], res["Wns"] if self.packed else None, cov=cov, corrected=corrected,
+                                                 wquantiles=wprobs, hist=hist)
+        self._stream()
+        th, _, dl = self.state
+        X = torch.zeros((self.N, self.ops.blob_width()), dtype=torch.float64, device=self.device)
+        redo = torch.empty_like(dl)
+        self.ops.blob_eval(th, self.stamp[self.cur], X, redo)
+        if not torch.equal(redo.view(torch.int64), dl.view(torch.int64)):
+            raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
+        del redo
+        wns = self.wns if self.packed else None
+        mean, S, W, Q, n_pos = self.ops.columns_moments(X, wns, m=nb, want_second=cov)
+        wq = M = n_mass = None
+        if wprobs:
+            q, M, n_mass = self.ops.columns_wquantiles(X, wns, wprobs, m=nb)
+            wq = np.ascontiguousarray(q.T)
+        h = None
+        if hist is not None and hist is not False:
+            cols, bins, rng_, pairs, bins2 = hist_opts
+            lo_hi, mass1, tallies1, mass2, outside2, M, n_mass = self.ops.columns_histograms(
+                X, wns, m=nb, columns=cols, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
+            h = _summary.make_hist(cols, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
+        del X
+        return _summary.make_summary(mean, S, W, Q, n_pos, np.empty((0, nb)), (), corrected, wq, wprobs, M, n_mass, h)
 
     def _to_host(self, tensors):
         """device tensors -> numpy arrays.  On the GPU: contiguous copies into PINNED host memory, all enqueued back to back on

@@ -102,11 +102,12 @@ def _check(cond: bool, msg: str) -> None:
         raise ValueError(msg)  # the reference raises ErrorException via error(...)
 
 
-def _summary_options(summary, download, sample=None):
-    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None (``sample``: the drivers' keyword
-    of that name -- with it the result is not empty either)"""
+def _summary_options(summary, download, sample=None, predictive=None):
+    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None (``sample``, ``predictive``: the
+    drivers' keywords of those names -- with either the result is not empty either)"""
     if summary is None or summary is False:
-        _check(bool(download) or sample is not None, "download=False needs summary: the result would be empty")
+        _check(bool(download) or sample is not None or predictive is not None,
+               "download=False needs summary: the result would be empty")
         return None
     from .summary import summary_options
 
@@ -120,6 +121,16 @@ def _sample_options(sample):
     from .summary import sample_options
 
     return sample_options(sample)
+
+
+def _predictive_options(predictive):
+    """the drivers' ``predictive`` keyword (True, or a dict of cov / corrected / wquantiles / hist) -> keywords of
+    posterior_predictive, or None"""
+    if predictive is None or predictive is False:
+        return None
+    from .summary import predictive_options
+
+    return predictive_options(predictive)
 
 
 def _make_engine(spec: ModelSpec, nparticles: int, engine, process_group, storage: str = "packed"):
@@ -142,7 +153,7 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
              ABCk=IndicatorStrict0toϵ, facc_stop: float = 0.0, facc_min: float = 0.0, facc_tune: float = 0.975,
              verbose: bool = True, verboseout: bool = True, rng: int = 1, parallel: bool = False,
              engine=None, process_group=None, max_iters: int = 1_000_000, resume=None, summary=None, download: bool = True,
-             sample=None):
+             sample=None, predictive=None):
     """Run ABC with differential-evolution moves in an SMC setup (src/abcdez_smc.jl:215).
 
     Same positional arguments, keywords and defaults as the reference, except:
@@ -167,9 +178,15 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     Posterior sample: ``sample=n`` (or ``dict(n=, draw=0, blobs=None)``) puts n equally weighted draws from the final weighted
     population into ``r.sample`` (:meth:`PopulationEngine.posterior_sample`: ``P``, ``index``, ``C``, ``blobs``, ``M``, ``n_mass``),
     drawn and gathered where the population lives -- ``r.sample.P`` is ``r.P[r.sample.index]`` without the download.
+
+    Posterior predictive: ``predictive=True`` (or a dict of the options ``cov``, ``corrected``, ``wquantiles``, ``hist`` of
+    :meth:`PopulationEngine.posterior_predictive`) puts the weighted mean and, with ``wquantiles=(0.025, 0.5, 0.975)``, the credible
+    bands of the accepted SIMULATIONS per observation into ``r.predictive`` -- the summaries of ``r.blobs`` under ``r.Wns``, computed
+    where the population lives; it needs a simulator with blobs and, like ``summary`` and ``sample``, goes with ``download=False``.
     """
     smp_opts = _sample_options(sample)
-    sum_opts = _summary_options(summary, download, sample)
+    prd_opts = _predictive_options(predictive)
+    sum_opts = _summary_options(summary, download, sample, prd_opts)
     # ---- initialisation / validation: src/abcdez_smc.jl:223-235
     _check(0.0 <= α < 1.0, "α must be in 0 <= α < 1")
     _check(0.0 <= δess <= 1.0, "δess must be in 0 <= δess <= 1")
@@ -294,6 +311,10 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
         from .summary import engine_sample
 
         out.sample = engine_sample(eng, **smp_opts)
+    if prd_opts is not None:
+        from .summary import engine_predictive
+
+        out.predictive = engine_predictive(eng, **prd_opts)
     out.eps = ϵ
     out.iters, out.nsims, out.updates = iters, nsims, updates
     out.engine = eng

@@ -501,3 +501,45 @@ def engine_summary(eng, **opts):
         return eng.posterior_summary(**opts)
     res = eng.result()
     return summary_reference(res["P"], res.get("Wns"), **opts)
+
+
+# ------------------------------------------------------------------ posterior predictive (include/abcdez_spec.h, "column summaries")
+PREDICTIVE_OPTIONS = ("cov", "corrected", "wquantiles", "hist")
+PREDICTIVE_NEEDS_BLOBS = "predictive: needs a simulator that returns blobs (blobs=True)"
+
+
+def predictive_options(predictive) -> dict:
+    """the ``predictive=`` keyword of the drivers: True, or a dict of cov / corrected / wquantiles / hist -> the keywords of
+    posterior_predictive"""
+    if predictive is True:
+        return {}
+    if isinstance(predictive, dict):
+        bad = set(predictive) - set(PREDICTIVE_OPTIONS)
+        if bad:
+            raise ValueError(f"predictive: unknown option(s) {sorted(bad)} (cov, corrected, wquantiles, hist)")
+        return dict(predictive)
+    raise ValueError("predictive must be None, True or a dict of the options cov, corrected, wquantiles, hist")
+
+
+def predictive_reference(blobs, Wns=None, cov=False, corrected=True, wquantiles=(), hist=None):
+    """numpy restatement of the posterior predictive summary: :func:`summary_reference` of the simulated data ``blobs`` (``r.blobs``:
+    (N,) for one number per particle, else (N, n_blob)) under the weights ``Wns`` (``r.Wns``; None: unit weights, abcdemc).  The
+    values are taken as they are; rows of particles without weight may hold anything.  ``quantiles`` of the record is empty."""
+    if blobs is None:
+        raise ValueError(PREDICTIVE_NEEDS_BLOBS)
+    X = np.asarray(blobs, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    if X.ndim != 2:
+        raise ValueError("predictive: blobs must be one row of numbers per particle")
+    return summary_reference(X, Wns, cov=cov, corrected=corrected, quantiles=(), wquantiles=wquantiles, hist=hist)
+
+
+def engine_predictive(eng, **opts):
+    """``eng.posterior_predictive(**opts)`` for a PopulationEngine; any other engine object: the restatement on its result"""
+    if hasattr(eng, "posterior_predictive"):
+        return eng.posterior_predictive(**opts)
+    res = eng.result()
+    if res.get("blobs") is None:
+        raise ValueError(PREDICTIVE_NEEDS_BLOBS)
+    return predictive_reference(res["blobs"], res.get("Wns"), **opts)

@@ -141,7 +141,8 @@ ABCDEZ_API int abcdez_init(abcdez_ctx* ctx, double* theta, double* logpi, double
  * the (logpi, nlogpi)-style entry points use them alongside, the packed sweeps update stamp_cur in place; NULL,
  * NULL = off).  abcdez_blob_eval re-runs that one simulator call for each of N particles on dense current rows
  * theta[N][ld] and writes blob[N][width] (abcdez_blob_width: ld for the MVN simulator, n_blob otherwise) and the
- * distance of the re-run, which must equal the stored distance bit for bit.                                    */
+ * distance of the re-run, which must equal the stored distance bit for bit.  A select enqueued ahead survives
+ * the call unless delta_out overlaps the distance array it was armed on (library version 660).                 */
 ABCDEZ_API int abcdez_ctx_set_stamps(abcdez_ctx* ctx, uint64_t* stamp_cur, uint64_t* stamp_nxt);
 ABCDEZ_API int abcdez_blob_width(abcdez_ctx* ctx, int32_t* width);
 ABCDEZ_API int abcdez_blob_eval(abcdez_ctx* ctx, const double* theta, const uint64_t* stamp, int64_t N, double* blob,
@@ -484,6 +485,41 @@ ABCDEZ_API int abcdez_posterior_sample(abcdez_ctx* ctx, const uint32_t* bits, in
                                        const double* wns, int64_t n, uint32_t draw, const double* delta, const uint64_t* stamp,
                                        uint32_t* idx_out, double* P_out, double* theta_out, double* delta_out, uint64_t* stamp_out,
                                        uint64_t* M, int64_t* n_mass);
+
+/* R2  Column summaries / posterior predictive (library version 660): the summaries of R1 for ANY dense per-particle matrix under
+ *     the population's weights -- made for the other half of the result tuple, the simulated data behind the particles (the
+ *     reference's blobs, docs/src/index.md:298-324): weighted mean and credible bands of the accepted simulations per observation,
+ *     summarised the way test/runtests.jl:159-162 summarises the parameters, a few hundred numbers instead of N x n_blob doubles.
+ *     Arithmetic: abcdez_spec.h, "posterior summaries" (column summaries): that of R1 value for value, the values taken as they
+ *     are (no push_p).  The matrix: X[N][ldx] (DEVICE, row-major; what abcdez_blob_eval writes with ldx = abcdez_blob_width), its
+ *     first m columns are the values, 1 <= m <= 256, ldx >= m (any ldx, odd ones included); wns = the weights (DEVICE, N doubles) or
+ *     NULL: every weight is 1.  Rows of positions that do not count (w <= 0, or no mass) are never read.  All three only read X
+ *     and wns; their scratch is the summaries' buffer, so a select enqueued ahead and every other state of the context survive
+ *     them: a run continued afterwards is bit-identical to one without them.
+ *     columns_moments (docs/src/index.md:298-324, test/runtests.jl:159-162): mean[m] and, if want_second, S[m*m] (row-major,
+ *       symmetric; else may be NULL) into HOST arrays, W = sum(wns), Q = sum(wns.^2), n_pos = #(wns > 0), exactly as
+ *       posterior_moments.  Fails when no weight is positive.                                                              */
+ABCDEZ_API int abcdez_columns_moments(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,
+                                      int32_t want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
+/*     columns_wquantiles (docs/src/index.md:298-324, test/runtests.jl:159-162): the weighted marginal quantiles of the columns
+ *       k0 .. k0 + nk - 1 (k0 + nk <= m) at probs[n_probs] (HOST, each in [0, 1]) over the resampler's integer masses, exactly as
+ *       posterior_wquantiles: q_out (HOST, nk x n_probs, [k - k0][q]), *M the total mass, *n_mass the number of positions that
+ *       count; all columns and probabilities in one call with one read-back.  Fails when no position carries mass and when the
+ *       total mass would reach 2^63 (weights that were never normalised).                                                  */
+ABCDEZ_API int abcdez_columns_wquantiles(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,
+                                         int32_t k0, int32_t nk, const double* probs, int32_t n_probs, double* q_out, uint64_t* M,
+                                         int64_t* n_mass);
+/*     columns_histograms (docs/src/index.md:298-324, test/runtests.jl:159-162): marginal and pairwise histograms of the columns
+ *       cols[n_cols] (HOST, strictly increasing in 0 .. m - 1; NULL: the columns 0 .. n_cols - 1), exactly as
+ *       posterior_histograms: bins (1 .. 4096), range (HOST, n_cols x 2) or NULL for the automatic range over the counting
+ *       positions (a constant column: +- 0.5), pairs[n_pairs][2] (HOST, j < k, both requested, each once; may be 0) with bins2
+ *       (1 .. 128) per axis; outputs, all HOST, lo_hi[n_cols][2], mass1[n_cols][bins], tallies1[n_cols][3] = (under, over, NaN),
+ *       mass2[n_pairs][bins2][bins2], outside2[n_pairs], *M, *n_mass.  Fails when no position carries mass, when the total mass
+ *       would reach 2^63, and when an automatic range is not usable (the message names the column: pass a range).          */
+ABCDEZ_API int abcdez_columns_histograms(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,
+                                         const int32_t* cols, int32_t n_cols, int32_t bins, const double* range,
+                                         const int32_t* pairs, int32_t n_pairs, int32_t bins2, double* lo_hi, uint64_t* mass1,
+                                         uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass);
 
 /* Test hooks: evaluate the spec arithmetic on the device (fn: 0 log, 1 exp, 2 sincos2pi,
  * 3 rint, 4 floor, 5 sqrt, 6 x/y2, 7 table log, 8 table sincos2pi, 9 sqrt_pn, 10 lgamma,

@@ -975,7 +975,19 @@ ABZ_HD double abz_tree_sum_small(const double* x, int p2) { /* p2 = power of two
  *   max(0, floor(m_i / (q + 1)) - 1) and at most ceil(m_i / q) + 1 times.  With equal masses m and n = k n_mass, q = floor(m / k).  When k divides m
  *   (always for k = 1; for the unit masses 2^b whenever k is a power of two) r = 0, every counting position holds exactly k whole
  *   strata and is drawn exactly k times; for k = 1 the sample is the identity over the counting positions.  When k does not divide m
- *   the first r strata are one point wider, a stratum can straddle two positions, and only the two bounds above hold. */
+ *   the first r strata are one point wider, a stratum can straddle two positions, and only the two bounds above hold.
+ *
+ * COLUMN SUMMARIES / POSTERIOR PREDICTIVE (the summaries above for the other half of a result, the simulated data behind the
+ * particles -- the reference's blobs, docs/src/index.md:298-324 -- or any other dense per-particle matrix).  No new arithmetic:
+ *   The matrix X has one row per position, N x m values (1 <= m <= 256) at a row stride ldx >= m; the weights w are those of the
+ *   population (or none: unit weights).  Read "x_ik" as X[i][k] TAKEN AS IT IS wherever the texts above say "the push_p cast of
+ *   component k of the current row of position i", and m wherever they say d = length(prior): moments (mean, S, W, Q, n_pos: the
+ *   same tile tree over the positions, abz_summary_term1 / abz_summary_term2, no fma, a position with w <= 0 contributes +0.0 and
+ *   its row is never read), weighted quantiles (the same integer masses m_i, the same rank rule and interpolation, M and n_mass),
+ *   histograms (abz_hist_bin, the automatic range over the counting positions, the tallies under / over / NaN / outside2) --
+ *   value for value, with the same limits and the same refusals.  The unweighted type-7 quantiles are not part of it.
+ *   The posterior predictive summary of a run is this with X = the blobs of the N positions of the current generation, rebuilt
+ *   from their stamps (the re-run distance must be the stored one, bit for bit), columns 0 .. n_blob - 1, under Wns. */
 ABZ_HD uint64_t abz_sample_point(uint64_t seed, uint32_t s, uint32_t draw, uint64_t q, uint64_t r) {
   const uint64_t a = (uint64_t)s * q + ((uint64_t)s < r ? (uint64_t)s : r);
   const uint64_t h = q + ((uint64_t)s < r ? 1u : 0u);

@@ -572,6 +572,70 @@ function posterior_sample(e::Engine; n::Integer, draw::Integer=0, packed::Bool=t
         devfree(idx); devfree(P); devfree(Δo)
     end
 end
+# ---- posterior predictive: the summaries above for the SIMULATED DATA behind the particles (the blobs, docs/src/index.md:298-324)
+# instead of the parameters (include/abcdez_spec.h "column summaries"; library version 660): weighted mean, covariance, credible
+# bands and histograms of the accepted simulations per observation.  The blobs of all N particles are rebuilt on the device from
+# their stamps as in `download` (the re-run distance must be the stored one), summarised there under the weights and freed: it
+# needs N * blob_width * 8 bytes of device memory while it runs and only the summary travels.  cov / corrected / wquantiles / hist
+# as in posterior_summary (column indices 0 .. n_blob - 1); packed = false: abcdemc's rows, every particle counts once.
+function posterior_predictive(e::Engine; packed::Bool=true, cov::Bool=false, corrected::Bool=true, wquantiles=Float64[], hist=nothing)
+    ccall((:abcdez_version, LIB), Cint, ()) >= 660 || error("ABCdeZHIP: posterior_predictive needs libabcdez_hip.so version 660 or later (rebuild the library)")
+    e.nb > 0 || error("predictive: needs a simulator that returns blobs (blobs=True)")
+    m = e.nb
+    wd = Ref(Int32(0)); check(ccall((:abcdez_blob_width, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), e.ctx, wd))
+    ldx = Int(wd[])
+    rows = devalloc(8 * e.N * e.ld); X = devalloc(8 * e.N * ldx); redo = devalloc(8e.N)
+    try
+        if packed
+            check(ccall((:abcdez_packed_gather, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        e.ctx, e.bits[e.bc], e.N, e.slot[1], e.slot[2], rows))
+        end
+        src = packed ? rows : e.slot[e.cur]
+        check(ccall((:abcdez_blob_eval, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                    e.ctx, src, e.stamp[e.cur], e.N, X, redo))
+        check(ccall((:abcdez_sync, LIB), Cint, (Ptr{Cvoid},), e.ctx))
+        R = Vector{Float64}(undef, e.N); Δ = Vector{Float64}(undef, e.N)
+        d2h(e, R, redo, 8e.N); d2h(e, Δ, e.delta[e.cur], 8e.N)
+        reinterpret(UInt64, R) == reinterpret(UInt64, Δ) || error("blobs: a re-run simulation does not reproduce the stored distance")
+        w = packed ? e.wns : C_NULL
+        mean = Vector{Float64}(undef, m); S = Matrix{Float64}(undef, m, m)
+        W = Ref(0.0); Q = Ref(0.0); npos = Ref(Int64(0))
+        check(ccall((:abcdez_columns_moments, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Float64}, Ref{Int64}),
+                    e.ctx, X, ldx, m, w, e.N, cov ? 1 : 0, mean, S, W, Q, npos))
+        wprobs = collect(Float64, wquantiles); wq = Matrix{Float64}(undef, length(wprobs), m)     # column-major: [q, k] = the library's [k][q]
+        M = UInt64[0]; nmass = Ref(Int64(0))
+        if !isempty(wprobs)
+            check(ccall((:abcdez_columns_wquantiles, LIB), Cint,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{UInt64}, Ref{Int64}),
+                        e.ctx, X, ldx, m, w, e.N, 0, m, wprobs, length(wprobs), wq, M, nmass))
+        end
+        h = nothing
+        if hist !== nothing
+            bins = Int(get(hist, :bins, 64)); bins2 = Int(something(get(hist, :bins2, nothing), min(bins, 128)))
+            pr = get(hist, :pairs, nothing)
+            pl = pr === nothing ? Tuple{Int,Int}[] : pr === :all ? [(j, k) for j in 0:m-1 for k in j+1:m-1] : collect(pr)
+            pairs = Int32[x for p in pl for x in p]; np = length(pl)
+            rg = get(hist, :range, nothing)
+            range = rg === nothing ? C_NULL : rg isa Tuple ? repeat(Float64[rg[1], rg[2]], m) : collect(Float64, permutedims(rg))
+            lohi = Matrix{Float64}(undef, 2, m); mass1 = Matrix{UInt64}(undef, bins, m); tallies = Matrix{UInt64}(undef, 3, m)
+            mass2 = Array{UInt64}(undef, bins2, bins2, np); outside2 = Vector{UInt64}(undef, np)   # column-major: [b_k, b_j, pair]
+            check(ccall((:abcdez_columns_histograms, LIB), Cint,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64, Ptr{Int32}, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Int32, Int32,
+                         Ptr{Float64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ref{Int64}),
+                        e.ctx, X, ldx, m, w, e.N, C_NULL, m, bins, range, np > 0 ? pairs : C_NULL, np, bins2,
+                        lohi, mass1, tallies, np > 0 ? mass2 : C_NULL, np > 0 ? outside2 : C_NULL, M, nmass))
+            h = (lo = lohi[1, :], hi = lohi[2, :], bins = bins, mass1 = mass1, under = tallies[1, :], over = tallies[2, :], nan = tallies[3, :],
+                 pairs = pl, bins2 = bins2, mass2 = mass2, outside2 = outside2, M = M[1], n_mass = Int(nmass[]))
+        end
+        den = corrected ? W[] - Q[] / W[] : W[]
+        return (mean = mean, cov = cov ? S ./ den : nothing, W = W[], ess = W[] * W[] / Q[], n_pos = Int(npos[]),
+                wquantiles = wq, M = (isempty(wprobs) && hist === nothing) ? nothing : M[1],
+                n_mass = (isempty(wprobs) && hist === nothing) ? nothing : Int(nmass[]), hist = h)
+    finally
+        devfree(rows); devfree(X); devfree(redo)
+    end
+end
 # the drivers' `summary` keyword: true, or a NamedTuple of the options above, e.g. (quantiles = [0.025, 0.975],)
 summary_of(e, summary; packed::Bool) = summary === nothing ? nothing :
     posterior_summary(e; packed = packed, (summary === true ? NamedTuple() : summary)...)
