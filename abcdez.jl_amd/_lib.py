@@ -106,6 +106,8 @@ PROTOTYPES = {
     "abcdez_columns_wquantiles": [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _i32, _vp, C.POINTER(C.c_uint64), _pi64],
     "abcdez_columns_histograms": [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                   C.POINTER(C.c_uint64), _pi64],
+    "abcdez_adjust_cross": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp],
+    "abcdez_adjust_apply": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32],
     "abcdez_math_eval": [_vp, C.c_int, _vp, _vp, _vp, _i64],
     "abcdez_draws_eval": [_vp, C.c_int, _i64, _i64, _i64, _u32, _f64, _f64, _vp, _vp, _vp, _vp],
 }
@@ -115,11 +117,12 @@ HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _i64)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _i64, _i32, _i32)
 # symbols with a non-status return type
 OTHER_SYMBOLS = ("abcdez_version", "abcdez_rng_rounds", "abcdez_last_error", "abcdez_abi_layout")
-# added after MIN_VERSION (versions 620, 630, 640, 650, 660): probed for, so that a 610 library still loads -- HipOps then lacks the
-# device summaries, a 640 library the device sample, a 650 library the column summaries (posterior predictive)
+# added after MIN_VERSION (versions 620, 630, 640, 650, 660, 670): probed for, so that a 610 library still loads -- HipOps then lacks
+# the device summaries, a 640 library the device sample, a 650 library the column summaries (posterior predictive), a 660 library
+# the regression adjustment
 OPTIONAL_SYMBOLS = ("abcdez_posterior_moments", "abcdez_posterior_quantiles", "abcdez_posterior_wquantiles",
                     "abcdez_posterior_histograms", "abcdez_posterior_sample", "abcdez_columns_moments", "abcdez_columns_wquantiles",
-                    "abcdez_columns_histograms")
+                    "abcdez_columns_histograms", "abcdez_adjust_cross", "abcdez_adjust_apply")
 
 
 class AbcdezError(RuntimeError):

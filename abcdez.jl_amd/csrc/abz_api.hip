@@ -108,10 +108,10 @@ extern "C" {
 
 /* 400: Philox4x32-10 again, abz_model.mv, group abort; 401: abcdemc's better particle by rejection;
  * 500: abcdez_comm_* and abcdez_smc_sweeps_sharded (RCCL behind the ABI), timing mode 3; 600: abcdez_comm_init_host (a host-supplied
- * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms; 650: abcdez_posterior_sample; 660: abcdez_columns_moments / _wquantiles / _histograms.  Hosts refuse a library older than the
+ * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms; 650: abcdez_posterior_sample; 660: abcdez_columns_moments / _wquantiles / _histograms; 670: abcdez_adjust_cross / _apply.  Hosts refuse a library older than the
  * header they were written against (abcdez.jl_amd/_lib.py, julia/ABCdeZHIP.jl check_abi): a signature that grew an argument links
  * against an old binary without a diagnostic. */
-int abcdez_version(void) { return 660; }
+int abcdez_version(void) { return 670; }
 int abcdez_rng_rounds(void) { return ABZ_PHILOX_ROUNDS; }
 
 /* sizeof / offsetof of the two structs that cross the boundary, so that a host that mirrors them by hand (the Julia
@@ -1639,6 +1639,39 @@ int abcdez_columns_histograms(abcdez_ctx* ctx, const double* X, int32_t ldx, int
   if (histogram_args("columns_histograms", m, "m", "columns", cols, n_cols, bins, range, pairs, n_pairs, bins2, mass2, outside2)) return -1;
   return abz_columns_histograms_impl(ctx, v, cols, n_cols, bins, range, pairs, n_pairs, bins2, lo_hi, mass1, tallies1, mass2, outside2, M,
                                      n_mass);
+}
+
+/* Regression adjustment (csrc/abz_adjust.hip): the two device passes of the local-linear ABC adjustment, relating the parameter rows
+ * to the simulated data behind them.  Like their neighbours they only read the population and Sb, and their scratch is the
+ * summaries' buffer.  Every refusal goes under the prefix "adjust:". */
+static int adjust_args(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                       const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols, bool rest, SumPop* p) {
+  if (posterior_pop("adjust", ctx, bits, N, slot0, slot1, wns, Sb && rest, p)) return -1;
+  ABZ_REQUIRE(lds >= 1, "adjust: lds must be at least 1");
+  ABZ_REQUIRE(n_cols >= 1 && n_cols <= ABZ_ADJUST_MAX_C && n_cols <= lds, "adjust: the columns must be 1 <= n_cols <= min(lds, 256)");
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const int32_t k = cols ? cols[c] : c;
+    ABZ_REQUIRE(k >= 0 && k < lds && (c == 0 || k > (cols ? cols[c - 1] : c - 1)),
+                "adjust: the columns must be strictly increasing in 0 .. lds - 1");
+  }
+  return 0;
+}
+
+int abcdez_adjust_cross(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                        const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols, const double* s_mean, const double* x_mean,
+                        double* S_sx_out) {
+  SumPop p;
+  if (adjust_args(ctx, bits, N, slot0, slot1, wns, Sb, lds, cols, n_cols, s_mean && x_mean && S_sx_out, &p)) return -1;
+  return abz_adjust_cross_impl(ctx, p, Sb, lds, cols, n_cols, s_mean, x_mean, S_sx_out);
+}
+
+int abcdez_adjust_apply(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                        const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols, const double* target, const double* beta,
+                        double* Y, int32_t ldy) {
+  SumPop p;
+  if (adjust_args(ctx, bits, N, slot0, slot1, wns, Sb, lds, cols, n_cols, target && beta && Y, &p)) return -1;
+  ABZ_REQUIRE(ldy >= p.d, "adjust: ldy must be at least length(prior)");
+  return abz_adjust_apply_impl(ctx, p, Sb, lds, cols, n_cols, target, beta, Y, ldy);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

@@ -1,5 +1,5 @@
-/* abz_summary.h -- what the posterior calls share (abz_summary.hip, abz_wquantile.hip, abz_hist.hip, abz_sample.hip, abz_columns.hip
- * and their entry points in abz_api.hip): the view of a population, the current row and the integer mass of a position, the tally
+/* abz_summary.h -- what the posterior calls share (abz_summary.hip, abz_wquantile.hip, abz_hist.hip, abz_sample.hip, abz_columns.hip,
+ * abz_adjust.hip and their entry points in abz_api.hip): the view of a population, the current row and the integer mass of a position, the tally
  * of the masses and its verdict, the calls' buffer in the context, and the drivers of the passes that do not depend on where the
  * values come from (the population's parameter rows, or any dense per-particle matrix: abz_columns.hip). */
 #pragma once
@@ -32,6 +32,7 @@ struct ColView {
 };
 
 #define ABZ_COLS_MAX_M 256  /* columns of a ColView at most (the second-moment pass keeps 4 x m x 4 sums in LDS) */
+#define ABZ_ADJUST_MAX_C 256  /* blob columns of a regression adjustment at most (abz_adjust.hip stages 256 x 8 coefficients in LDS) */
 #define WQ_CB 16            /* weighted quantiles: columns per chunk, 128 bytes of a row */
 #define H_RC 8              /* histograms, range: columns per launch (64 bytes of a row; 16 spill scalar registers) */
 
@@ -109,6 +110,10 @@ int abz_histograms_drive(abcdez_ctx*, const char* call, int64_t N, int d, const 
                          int bins, const double* range, const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1,
                          uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass);
 
+/* the upper levels of the tile tree for `ntrees` trees of n partials each, parts[b n .. (b + 1) n) -> out[b] (sum_finish_kernel,
+ * enqueued on the context's stream; no division) */
+int abz_sum_finish(abcdez_ctx*, const double* parts, int64_t n, double* out, unsigned ntrees);
+
 int abz_posterior_moments_impl(abcdez_ctx*, const SumPop&, int want_second, double* mean, double* S, double* W, double* Q, int64_t* n_pos);
 int abz_posterior_quantiles_impl(abcdez_ctx*, const SumPop&, int k, const double* probs, int n_probs, double* q_out);
 int abz_posterior_wquantiles_impl(abcdez_ctx*, const SumPop&, int k0, int nk, const double* probs, int n_probs, double* q_out, uint64_t* M,
@@ -126,3 +131,8 @@ int abz_columns_wquantiles_impl(abcdez_ctx*, const ColView&, int k0, int nk, con
 int abz_columns_histograms_impl(abcdez_ctx*, const ColView&, const int32_t* cols, int n_cols, int bins, const double* range,
                                 const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
                                 uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass);
+/* abz_adjust.hip: s_mean[c], x_mean[d], target[c], beta[c d], S_sx_out[c d] are HOST arrays, Sb and Y DEVICE matrices */
+int abz_adjust_cross_impl(abcdez_ctx*, const SumPop&, const double* Sb, int lds, const int32_t* cols, int c, const double* s_mean,
+                          const double* x_mean, double* S_sx_out);
+int abz_adjust_apply_impl(abcdez_ctx*, const SumPop&, const double* Sb, int lds, const int32_t* cols, int c, const double* target,
+                          const double* beta, double* Y, int ldy);

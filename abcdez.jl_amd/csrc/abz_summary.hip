@@ -250,6 +250,13 @@ int sum_mass_verdict(const char* call, unsigned long long lo, unsigned long long
   return 0;
 }
 
+int abz_sum_finish(abcdez_ctx* ctx, const double* parts, int64_t n, double* out, unsigned ntrees) {
+  SumFinishArgs f{parts, n, out, 0, 0};
+  hipLaunchKernelGGL(sum_finish_kernel, dim3(ntrees), dim3(ABZ_BLOCK), 0, ctx->stream, f);
+  ABZ_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int abz_moments_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const SumMomentsGather& src, int want_second, double* mean,
                       double* S, double* W, double* Q, int64_t* n_pos) {
   const size_t nt = (size_t)((N + ABZ_TILE - 1) / ABZ_TILE);

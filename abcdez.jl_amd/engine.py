@@ -603,6 +603,47 @@ class HipOps:
             C.byref(M), C.byref(n_mass)))
         return lo_hi, mass1, tallies1, mass2, outside2, M.value, n_mass.value
 
+    # ---- regression adjustment: the two device passes between the parameter rows and the blobs (include/abcdez_hip.h, R3) ----
+    @staticmethod
+    def _adjust_blobs(Sb, columns):
+        """(lds, cols int32[c]) of the device blob matrix Sb[N][lds] and the chosen columns (None: all)"""
+        if Sb.dim() != 2 or Sb.dtype != torch.float64 or not Sb.is_contiguous():
+            raise ValueError("adjust: Sb must be a contiguous float64 matrix N x lds")
+        lds = int(Sb.shape[1])
+        cols = np.arange(lds, dtype=np.int32) if columns is None else np.ascontiguousarray(columns, dtype=np.int32).reshape(-1)
+        return lds, cols
+
+    def adjust_cross(self, bits, slot0, slot1, wns, N, Sb, columns, s_mean, x_mean):
+        """S_sx[c, d]: the weighted second central moments between the blob columns ``columns`` of the device matrix Sb[N][lds] and
+        the push_p-cast parameters of the population, centred on the host vectors s_mean[c] and x_mean[d] (abcdez_adjust_cross)"""
+        lds, cols = self._adjust_blobs(Sb, columns)
+        sm = np.ascontiguousarray(s_mean, dtype=np.float64).reshape(-1)
+        xm = np.ascontiguousarray(x_mean, dtype=np.float64).reshape(-1)
+        if sm.size != cols.size or xm.size != self.spec.d:
+            raise ValueError("adjust: s_mean must hold one mean per chosen column and x_mean one per parameter")
+        out = np.empty((max(int(cols.size), 1), self.spec.d), dtype=np.float64)
+        _lib.check(self.lib, self._summary_fn("abcdez_adjust_cross", 670)(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), _ptr(Sb), lds, cols.ctypes.data, int(cols.size),
+            sm.ctypes.data, xm.ctypes.data, out.ctypes.data))
+        return out
+
+    def adjust_apply(self, bits, slot0, slot1, wns, N, Sb, columns, target, beta, Y=None):
+        """Y[N, d] (a DEVICE tensor; created when None): the adjusted rows x_i - beta^T (s_i - target) of the positions that count,
+        +0.0 for the others (abcdez_adjust_apply); ``target`` (c) and ``beta`` (c x d) are host arrays"""
+        lds, cols = self._adjust_blobs(Sb, columns)
+        t = np.ascontiguousarray(target, dtype=np.float64).reshape(-1)
+        b = np.ascontiguousarray(beta, dtype=np.float64)
+        if t.size != cols.size or b.shape != (cols.size, self.spec.d):
+            raise ValueError("adjust: target must hold one number per chosen column and beta be c x d")
+        if Y is None:
+            Y = torch.empty((int(N), self.spec.d), dtype=torch.float64, device=self.device)
+        if Y.dim() != 2 or Y.dtype != torch.float64 or not Y.is_contiguous() or Y.shape[0] != int(N):
+            raise ValueError("adjust: Y must be a contiguous float64 matrix N x ldy")
+        _lib.check(self.lib, self._summary_fn("abcdez_adjust_apply", 670)(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), _ptr(Sb), lds, cols.ctypes.data, int(cols.size),
+            t.ctypes.data, b.ctypes.data, _ptr(Y), int(Y.shape[1])))
+        return Y
+
     def set_stamps(self, cur, nxt):
         _lib.check(self.lib, self.lib.abcdez_ctx_set_stamps(self.ctx, _ptr(cur), _ptr(nxt)))
 
@@ -1538,6 +1579,81 @@ class PopulationEngine:
             h = _summary.make_hist(cols, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
         del X
         return _summary.make_summary(mean, S, W, Q, n_pos, np.empty((0, nb)), (), corrected, wq, wprobs, M, n_mass, h)
+
+    def posterior_adjusted(self, columns=None, target=None, ridge: float = 0.0, cov: bool = True, corrected: bool = True, wquantiles=(),
+                           hist=None, rows: bool = False):
+        """The regression-adjusted posterior (include/abcdez_spec.h, "REGRESSION ADJUSTMENT"): the local-linear ABC adjustment of
+        Beaumont, Zhang and Balding (2002) -- `loclinear` of R's abc, `adjust_posterior` of pyABC and ELFI.  Every accepted particle
+        is corrected for the gap between its simulation s_i (the blobs) and the observation, theta*_i = theta_i - beta^T (s_i -
+        target), beta being the weighted least-squares slope of the parameters on the chosen blob ``columns`` (default: all) under
+        the weights ``Wns``; ``target`` defaults to the simulator's data when they are one number per blob column, and is required
+        otherwise.  ``ridge`` >= 0 scales the diagonal of the normal equations by 1 + ridge (collinear columns are refused without
+        it).  Returns the record of :func:`abcdez_amd.summary.make_adjusted`: the fields of :meth:`posterior_summary` (``mean``,
+        ``cov``, ``S``, ``W``, ``Q``, ``ess``, ``n_pos``, ``wquantiles``, ``hist``; options as there) for the ADJUSTED parameters,
+        and ``beta`` (c x d), ``columns``, ``target``, ``ridge``, ``s_mean``, ``x_mean`` (the unadjusted mean), ``S_sx``; with
+        ``rows=True`` also ``P`` (N x d adjusted rows, +0.0 for particles without weight).
+
+        The adjustment does not keep a discrete parameter integer, and adjusted values may leave the prior's support (the method's
+        known caveat; transforms are the user's business).  The regression weights are the population's: kernel weights for an
+        Epanechnikov ABC kernel, uniform over the accepted particles for an indicator kernel.
+
+        On the HIP engine the blobs are rebuilt on the device as :meth:`posterior_predictive` does, the moments of both halves, the
+        cross moments (csrc/abz_adjust.hip) and the adjusted rows are computed there, the c x c solve runs on the host, and the
+        adjusted rows are summarised by the column summaries and freed -- bit for bit
+        :func:`abcdez_amd.summary.adjust_reference` of the downloaded result.  It needs N x (blob_width + d) x 8 bytes of device
+        memory for the two matrices while it runs, and changes nothing a continued run depends on.  Engines without the device
+        calls compute the restatement on ``result()``.  A simulator without blobs is refused."""
+        from . import summary as _summary
+
+        wprobs = tuple(float(p) for p in wquantiles)
+        if any(not 0.0 <= p <= 1.0 for p in wprobs):
+            raise ValueError("adjust: p must be in [0, 1]")
+        if not self.blob_on:
+            raise ValueError(_summary.ADJUST_NEEDS_BLOBS)
+        nb, d = self.spec.n_blob, self.spec.d
+        cols = _summary.adjust_columns(columns, nb)
+        t = _summary.adjust_target(target, cols, nb, tuple(self.spec.sim.data()))
+        ridge = _summary.adjust_ridge(ridge)
+        want_hist = hist is not None and hist is not False
+        if want_hist:
+            hist_opts = _summary.hist_options(hist, d)
+        if not hasattr(self.ops, "adjust_cross"):
+            res = self.result()
+            return _summary.adjust_reference(res["P"], res["blobs"], res["Wns"] if self.packed else None, target=t, columns=cols,
+                                             ridge=ridge, cov=cov, corrected=corrected, wquantiles=wprobs, hist=hist, rows=rows)
+        self._stream()
+        th, _, dl = self.state
+        Sb = torch.zeros((self.N, self.ops.blob_width()), dtype=torch.float64, device=self.device)
+        redo = torch.empty_like(dl)
+        self.ops.blob_eval(th, self.stamp[self.cur], Sb, redo)
+        if not torch.equal(redo.view(torch.int64), dl.view(torch.int64)):
+            raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
+        del redo
+        pop = self._live_population()
+        wns = self.wns if self.packed else None
+        x_mean = self.ops.posterior_moments(*pop, self.N, want_second=False)[0]
+        s_all, S_all = self.ops.columns_moments(Sb, wns, m=nb, want_second=True)[:2]
+        s_mean = s_all[cols]
+        _summary.adjust_check_means(s_mean, x_mean)
+        S_sx = self.ops.adjust_cross(*pop, self.N, Sb, cols, s_mean, x_mean)
+        beta = _summary.adjust_solve(S_all[np.ix_(cols, cols)], S_sx, ridge, cols)
+        Y = self.ops.adjust_apply(*pop, self.N, Sb, cols, t, beta)
+        del Sb
+        mean, S, W, Q, n_pos = self.ops.columns_moments(Y, wns, m=d, want_second=cov)
+        wq = M = n_mass = None
+        if wprobs:
+            q, M, n_mass = self.ops.columns_wquantiles(Y, wns, wprobs, m=d)
+            wq = np.ascontiguousarray(q.T)
+        h = None
+        if want_hist:
+            hc, bins, rng_, pairs, bins2 = hist_opts
+            lo_hi, mass1, tallies1, mass2, outside2, M, n_mass = self.ops.columns_histograms(
+                Y, wns, m=d, columns=hc, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
+            h = _summary.make_hist(hc, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
+        Ph = self._to_host([Y])[0] if rows else None
+        del Y
+        rec = _summary.make_summary(mean, S, W, Q, n_pos, np.empty((0, d)), (), corrected, wq, wprobs, M, n_mass, h)
+        return _summary.make_adjusted(rec, beta, cols, t, ridge, s_mean, x_mean, S_sx, Ph)
 
     def _to_host(self, tensors):
         """device tensors -> numpy arrays.  On the GPU: contiguous copies into PINNED host memory, all enqueued back to back on

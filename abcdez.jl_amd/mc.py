@@ -12,7 +12,7 @@ import math
 
 from .model import ModelSpec
 from .priors import prior_length
-from .smc import Result, _check, _make_engine, _predictive_options, _sample_options, _summary_options, load_checkpoint
+from .smc import Result, _adjust_options, _check, _make_engine, _predictive_options, _sample_options, _summary_options, load_checkpoint
 
 log = logging.getLogger("abcdez_amd")
 
@@ -20,7 +20,7 @@ log = logging.getLogger("abcdez_amd")
 def abcdemc(prior, dist, ϵ_target, varexternal=None, *,
             nparticles: int = 50, generations: int = 20, verbose: bool = True, rng: int = 1,
             parallel: bool = False, engine=None, process_group=None, resume=None, summary=None, download: bool = True, sample=None,
-            predictive=None):
+            predictive=None, adjust=None):
     """Run ABC with differential-evolution moves in an MCMC setup (src/abcdez_mc.jl:102).
 
     Same arguments and defaults as the reference (see :func:`abcdesmc` for the
@@ -30,10 +30,13 @@ def abcdemc(prior, dist, ϵ_target, varexternal=None, *,
     ``summary`` / ``download``: as in :func:`abcdesmc` (abcdemc has no weights: every particle counts once).
     ``sample=n | dict(n=, draw=, blobs=)``: as in :func:`abcdesmc`, ``r.sample`` (unit masses: the closed form of the spec).
     ``predictive=True | dict(cov=, corrected=, wquantiles=, hist=)``: as in :func:`abcdesmc`, ``r.predictive`` (unit weights).
+    ``adjust=True | dict(columns=, target=, ridge=, cov=, corrected=, wquantiles=, hist=, rows=)``: as in :func:`abcdesmc`,
+    ``r.adjusted`` (unit weights: an ordinary least-squares adjustment over all particles).
     """
     smp_opts = _sample_options(sample)
     prd_opts = _predictive_options(predictive)
-    sum_opts = _summary_options(summary, download, sample, prd_opts)
+    adj_opts = _adjust_options(adjust)
+    sum_opts = _summary_options(summary, download, sample, prd_opts, adj_opts)
     α = 0.0                                                   # mc:107
     _check(0.0 <= ϵ_target, "ϵ_target must be non-negative")  # mc:108
     _check(5 <= nparticles, "nparticles must be at least 5")  # mc:109
@@ -46,11 +49,11 @@ def abcdemc(prior, dist, ϵ_target, varexternal=None, *,
     # off by default: measured slower -- is switched on)
     with (eng.run_scope() if hasattr(eng, "run_scope") else contextlib.nullcontext()):
         return _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, resume, α, parallel, sum_opts, download,
-                            smp_opts, prd_opts)
+                            smp_opts, prd_opts, adj_opts)
 
 
 def _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, resume, α, parallel=False, sum_opts=None,
-                 download=True, smp_opts=None, prd_opts=None):
+                 download=True, smp_opts=None, prd_opts=None, adj_opts=None):
     if verbose:                                               # mc:113-114
         log.info("Running abcdemc! with executor %s (%d rank(s))", type(getattr(eng, "ops", eng)).__name__, getattr(eng, "world", 1))
         log.info("Running abcdemc! with ϵ_target=%s nparticles=%d generations=%d α=%s rng=%s parallel=%s", ϵ_target, nparticles,
@@ -114,6 +117,10 @@ def _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, 
         from .summary import engine_predictive
 
         out.predictive = engine_predictive(eng, **prd_opts)
+    if adj_opts is not None:
+        from .summary import engine_adjusted
+
+        out.adjusted = engine_adjusted(eng, **adj_opts)
     out.reached_eps = conv
     out.nsims, out.updates, out.complete = nsims, generations * nparticles, complete
     out.engine = eng

@@ -102,11 +102,11 @@ def _check(cond: bool, msg: str) -> None:
         raise ValueError(msg)  # the reference raises ErrorException via error(...)
 
 
-def _summary_options(summary, download, sample=None, predictive=None):
-    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None (``sample``, ``predictive``: the
-    drivers' keywords of those names -- with either the result is not empty either)"""
+def _summary_options(summary, download, sample=None, predictive=None, adjust=None):
+    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None (``sample``, ``predictive``,
+    ``adjust``: the drivers' keywords of those names -- with any of them the result is not empty either)"""
     if summary is None or summary is False:
-        _check(bool(download) or sample is not None or predictive is not None,
+        _check(bool(download) or sample is not None or predictive is not None or adjust is not None,
                "download=False needs summary: the result would be empty")
         return None
     from .summary import summary_options
@@ -133,6 +133,16 @@ def _predictive_options(predictive):
     return predictive_options(predictive)
 
 
+def _adjust_options(adjust):
+    """the drivers' ``adjust`` keyword (True, or a dict of columns / target / ridge / cov / corrected / wquantiles / hist / rows) ->
+    keywords of posterior_adjusted, or None"""
+    if adjust is None or adjust is False:
+        return None
+    from .summary import adjust_options
+
+    return adjust_options(adjust)
+
+
 def _make_engine(spec: ModelSpec, nparticles: int, engine, process_group, storage: str = "packed"):
     if engine is not None:
         if not callable(engine):
@@ -153,7 +163,7 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
              ABCk=IndicatorStrict0toϵ, facc_stop: float = 0.0, facc_min: float = 0.0, facc_tune: float = 0.975,
              verbose: bool = True, verboseout: bool = True, rng: int = 1, parallel: bool = False,
              engine=None, process_group=None, max_iters: int = 1_000_000, resume=None, summary=None, download: bool = True,
-             sample=None, predictive=None):
+             sample=None, predictive=None, adjust=None):
     """Run ABC with differential-evolution moves in an SMC setup (src/abcdez_smc.jl:215).
 
     Same positional arguments, keywords and defaults as the reference, except:
@@ -183,10 +193,17 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     :meth:`PopulationEngine.posterior_predictive`) puts the weighted mean and, with ``wquantiles=(0.025, 0.5, 0.975)``, the credible
     bands of the accepted SIMULATIONS per observation into ``r.predictive`` -- the summaries of ``r.blobs`` under ``r.Wns``, computed
     where the population lives; it needs a simulator with blobs and, like ``summary`` and ``sample``, goes with ``download=False``.
+
+    Regression adjustment: ``adjust=True`` (or a dict of the options ``columns``, ``target``, ``ridge``, ``cov``, ``corrected``,
+    ``wquantiles``, ``hist``, ``rows`` of :meth:`PopulationEngine.posterior_adjusted`) puts the local-linear regression-adjusted
+    posterior (Beaumont, Zhang and Balding 2002) into ``r.adjusted``: every accepted particle corrected for the gap between its
+    simulation and the observation, theta - beta^T (s - target), and summarised where the population lives.  A run may then stop
+    at a larger ϵ_target for the same accuracy.  It needs a simulator with blobs and goes with ``download=False``.
     """
     smp_opts = _sample_options(sample)
     prd_opts = _predictive_options(predictive)
-    sum_opts = _summary_options(summary, download, sample, prd_opts)
+    adj_opts = _adjust_options(adjust)
+    sum_opts = _summary_options(summary, download, sample, prd_opts, adj_opts)
     # ---- initialisation / validation: src/abcdez_smc.jl:223-235
     _check(0.0 <= α < 1.0, "α must be in 0 <= α < 1")
     _check(0.0 <= δess <= 1.0, "δess must be in 0 <= δess <= 1")
@@ -315,6 +332,10 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
         from .summary import engine_predictive
 
         out.predictive = engine_predictive(eng, **prd_opts)
+    if adj_opts is not None:
+        from .summary import engine_adjusted
+
+        out.adjusted = engine_adjusted(eng, **adj_opts)
     out.eps = ϵ
     out.iters, out.nsims, out.updates = iters, nsims, updates
     out.engine = eng

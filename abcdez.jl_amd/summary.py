@@ -543,3 +543,199 @@ def engine_predictive(eng, **opts):
     if res.get("blobs") is None:
         raise ValueError(PREDICTIVE_NEEDS_BLOBS)
     return predictive_reference(res["blobs"], res.get("Wns"), **opts)
+
+
+# ------------------------------------------------------------------ regression adjustment (include/abcdez_spec.h, "REGRESSION ADJUSTMENT")
+ADJUST_OPTIONS = ("columns", "target", "ridge", "cov", "corrected", "wquantiles", "hist", "rows")
+ADJUST_NEEDS_BLOBS = "adjust: needs a simulator that returns blobs (blobs=True)"
+ADJUST_MAX_C = 256              # ABZ_ADJUST_MAX_C
+ADJUST_PIVOT = 2.0 ** -40       # a pivot must exceed this fraction of its diagonal entry
+
+
+def adjust_options(adjust) -> dict:
+    """the ``adjust=`` keyword of the drivers: True, or a dict of columns / target / ridge / cov / corrected / wquantiles / hist /
+    rows -> the keywords of posterior_adjusted"""
+    if adjust is True:
+        return {}
+    if isinstance(adjust, dict):
+        bad = set(adjust) - set(ADJUST_OPTIONS)
+        if bad:
+            raise ValueError(f"adjust: unknown option(s) {sorted(bad)} (columns, target, ridge, cov, corrected, wquantiles, hist, rows)")
+        return dict(adjust)
+    raise ValueError("adjust must be None, True or a dict of the options columns, target, ridge, cov, corrected, wquantiles, hist, rows")
+
+
+def adjust_columns(columns, n_blob: int):
+    """the ``columns`` option -> a list of blob columns, strictly increasing in 0 .. n_blob - 1 (None: all)"""
+    cols = list(range(n_blob)) if columns is None else [int(c) for c in columns]
+    if not 1 <= len(cols) <= ADJUST_MAX_C or cols[0] < 0 or cols[-1] >= n_blob or any(a >= b for a, b in zip(cols, cols[1:])):
+        raise ValueError("adjust: columns must be strictly increasing blob columns in 0 .. n_blob - 1, at most 256 of them")
+    return cols
+
+
+def adjust_target(target, columns, n_blob: int, data=None):
+    """the ``target`` option -> the c doubles t: one per chosen column.  None: ``data`` (the simulator's ``data()``) when it has one
+    number per blob column, restricted to ``columns``; otherwise a target is required."""
+    if target is None:
+        if data is None or len(data) != n_blob:
+            raise ValueError("adjust: target is required (the simulator's data are not one number per blob column)")
+        t = np.asarray(data, dtype=np.float64)[list(columns)]
+    else:
+        t = np.atleast_1d(np.asarray(target, dtype=np.float64))
+        if t.shape != (len(columns),):
+            raise ValueError(f"adjust: target must hold {len(columns)} number(s), one per chosen blob column")
+    if not np.isfinite(t).all():
+        raise ValueError("adjust: the target is not finite")
+    return np.ascontiguousarray(t)
+
+
+def adjust_ridge(ridge) -> float:
+    r = float(ridge)
+    if not (0.0 <= r < math.inf):
+        raise ValueError("adjust: ridge must be finite and not negative")
+    return r
+
+
+ADJUST_NOT_FINITE = "adjust: a moment of the simulated data is not finite (a NaN or an infinity in the blobs of a particle that counts)"
+
+
+def adjust_check_means(s_mean, x_mean):
+    """the means both passes centre on must be finite: refused before the cross pass"""
+    if not (np.isfinite(s_mean).all() and np.isfinite(x_mean).all()):
+        raise ValueError(ADJUST_NOT_FINITE)
+
+
+def adjust_solve(S_ss, S_sx, ridge: float = 0.0, columns=None):
+    """The single solve of the regression adjustment (include/abcdez_spec.h, "REGRESSION ADJUSTMENT"), in plain double, literally:
+    ``S_ss`` (c x c: the second central moments of the chosen blob columns), ``S_sx`` (c x d) -> beta (c x d) with
+    (S_ss + ridge diag(S_ss)) beta = S_sx, by a row-by-row Cholesky factorisation and a forward and a back substitution per column,
+    every sum in ascending index from +0.0, no contraction.  ``columns`` only names the blob columns in the refusal."""
+    A = np.array(S_ss, dtype=np.float64)
+    B = np.array(S_sx, dtype=np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    c = A.shape[0]
+    if A.shape != (c, c) or B.shape[0] != c or c < 1:
+        raise ValueError("adjust: S_ss must be c x c and S_sx c x d")
+    ridge = adjust_ridge(ridge)
+    if not (np.isfinite(A).all() and np.isfinite(B).all()):
+        raise ValueError(ADJUST_NOT_FINITE)
+    names = list(range(c)) if columns is None else list(columns)
+    a = A.tolist()
+    for j in range(c):
+        a[j][j] = a[j][j] * (1.0 + ridge)
+    L = [[0.0] * c for _ in range(c)]
+    for j in range(c):
+        Lj = L[j]
+        for k in range(j):
+            Lk = L[k]
+            s = 0.0
+            for p in range(k):
+                s = s + Lj[p] * Lk[p]
+            Lj[k] = (a[j][k] - s) / Lk[k]
+        s = 0.0
+        for p in range(j):
+            s = s + Lj[p] * Lj[p]
+        r = a[j][j] - s
+        if not (math.isfinite(r) and r > ADJUST_PIVOT * a[j][j]):
+            raise ValueError(f"adjust: the simulated data are collinear or constant in column {names[j]}: pass `ridge` or fewer `columns`")
+        Lj[j] = math.sqrt(r)
+    Ln = np.array(L)
+    with np.errstate(over="ignore", invalid="ignore"):
+        Z = np.empty_like(B)                            # L z = b: every column k at once, element for element the scalar recurrence
+        for j in range(c):
+            s = np.zeros(B.shape[1])
+            for p in range(j):
+                s = s + Ln[j, p] * Z[p]
+            Z[j] = (B[j] - s) / Ln[j, j]
+        beta = np.empty_like(B)                         # L^T beta = z
+        for j in range(c - 1, -1, -1):
+            s = np.zeros(B.shape[1])
+            for p in range(j + 1, c):
+                s = s + Ln[p, j] * beta[p]
+            beta[j] = (Z[j] - s) / Ln[j, j]
+    if not np.isfinite(beta).all():
+        raise ValueError("adjust: a regression coefficient is not finite")
+    return beta
+
+
+def adjust_apply(X, B, live, target, beta):
+    """Y (N x d): row i = x_i - sum_j beta[j] (B[i, j] - target[j]), j ascending from +0.0, one subtraction, one multiplication and
+    one addition per term, for the rows with ``live``; +0.0 for the others, whose inputs are never read"""
+    Xl = np.where(live[:, None], X, 0.0)
+    Bl = np.where(live[:, None], B, 0.0)
+    acc = np.zeros_like(Xl)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(B.shape[1]):
+            acc = acc + beta[j][None, :] * (Bl[:, j] - target[j])[:, None]
+        return np.where(live[:, None], Xl - acc, 0.0)
+
+
+def make_adjusted(rec, beta, columns, target, ridge, s_mean, x_mean, S_sx, P=None):
+    """the record ``posterior_adjusted`` returns: the fields of :func:`make_summary` for the adjusted parameters (``rec``) and
+    ``beta`` (c x d), ``columns``, ``target``, ``ridge``, ``s_mean`` (c), ``x_mean`` (d: the unadjusted weighted mean), ``S_sx``
+    (c x d), ``P`` (N x d adjusted rows, +0.0 for particles without weight; None unless asked for)"""
+    c = len(columns)
+    out = SimpleNamespace(**vars(rec))
+    out.beta = np.asarray(beta, dtype=np.float64).reshape(c, -1)
+    out.columns = tuple(int(k) for k in columns)
+    out.target = np.asarray(target, dtype=np.float64).reshape(c)
+    out.ridge = float(ridge)
+    out.s_mean = np.asarray(s_mean, dtype=np.float64).reshape(c)
+    out.x_mean = np.asarray(x_mean, dtype=np.float64).reshape(-1)
+    out.S_sx = np.asarray(S_sx, dtype=np.float64).reshape(c, -1)
+    out.P = P
+    return out
+
+
+def adjust_reference(P, blobs, Wns=None, target=None, columns=None, ridge=0.0, cov=True, corrected=True, wquantiles=(), hist=None,
+                     rows=False, data=None):
+    """numpy restatement of the regression-adjusted posterior (include/abcdez_spec.h, "REGRESSION ADJUSTMENT"), literally: ``P``
+    the push_p-cast population (``r.P``), ``blobs`` the simulated data behind it (``r.blobs``), ``Wns`` the weights (None: unit
+    weights, abcdemc), ``target`` one number per chosen column (None: ``data``, the simulator's ``data()``, when it has one number
+    per blob column).  Moments by :func:`summary_reference`, the cross moments by :func:`tile_tree_sum`, the solve by
+    :func:`adjust_solve`, and the summaries of the adjusted rows by :func:`summary_reference` again.  Rows of particles without
+    weight may hold anything.  Returns the record of :func:`make_adjusted`."""
+    if blobs is None:
+        raise ValueError(ADJUST_NEEDS_BLOBS)
+    X = np.asarray(P, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    B = np.asarray(blobs, dtype=np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    if X.ndim != 2 or B.ndim != 2 or B.shape[0] != X.shape[0]:
+        raise ValueError("adjust: P and blobs must hold one row per particle")
+    N, d = X.shape
+    nb = B.shape[1]
+    cols = adjust_columns(columns, nb)
+    t = adjust_target(target, cols, nb, data)
+    ridge = adjust_ridge(ridge)
+    mx = summary_reference(X, Wns, cov=False)
+    ms = summary_reference(B, Wns, cov=True)
+    w = np.ones(N) if Wns is None else np.asarray(Wns, dtype=np.float64)
+    live = w > 0.0
+    wl = np.where(live, w, 0.0)
+    Bc = B[:, cols]
+    s_mean, x_mean = ms.mean[cols], mx.mean
+    adjust_check_means(s_mean, x_mean)
+    with np.errstate(over="ignore", invalid="ignore"):
+        Cs = np.where(live[:, None], Bc, 0.0) - s_mean
+        Cx = np.where(live[:, None], X, 0.0) - x_mean
+        S_sx = np.empty((len(cols), d))
+        for j in range(len(cols)):
+            S_sx[j] = tile_tree_sum(np.where(live[:, None], wl[:, None] * (Cs[:, j:j + 1] * Cx), 0.0))
+    beta = adjust_solve(ms.S[np.ix_(cols, cols)], S_sx, ridge, cols)
+    Y = adjust_apply(X, Bc, live, t, beta)
+    rec = summary_reference(Y, Wns, cov=cov, corrected=corrected, quantiles=(), wquantiles=wquantiles, hist=hist)
+    return make_adjusted(rec, beta, cols, t, ridge, s_mean, x_mean, S_sx, Y if rows else None)
+
+
+def engine_adjusted(eng, **opts):
+    """``eng.posterior_adjusted(**opts)`` for a PopulationEngine; any other engine object: the restatement on its result"""
+    if hasattr(eng, "posterior_adjusted"):
+        return eng.posterior_adjusted(**opts)
+    res = eng.result()
+    if res.get("blobs") is None:
+        raise ValueError(ADJUST_NEEDS_BLOBS)
+    return adjust_reference(res["P"], res["blobs"], res.get("Wns"), data=tuple(eng.spec.sim.data()), **opts)

@@ -521,6 +521,30 @@ ABCDEZ_API int abcdez_columns_histograms(abcdez_ctx* ctx, const double* X, int32
                                          const int32_t* pairs, int32_t n_pairs, int32_t bins2, double* lo_hi, uint64_t* mass1,
                                          uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M, int64_t* n_mass);
 
+/* R3  Regression adjustment (library version 670): the local-linear ABC adjustment of Beaumont, Zhang and Balding (2002),
+ *     theta*_i = theta_i - beta^T (s_i - s_obs) -- the `loclinear` method of R's abc, `adjust_posterior` of pyABC and ELFI -- where
+ *     the population and the simulated data behind it live.  Arithmetic: abcdez_spec.h, "posterior summaries" (REGRESSION
+ *     ADJUSTMENT).  Both calls take the population arguments of abcdez_posterior_moments and the dense blob matrix Sb[N][lds]
+ *     (DEVICE, row-major; what abcdez_blob_eval writes with lds = abcdez_blob_width), of which the columns cols[n_cols] (HOST,
+ *     strictly increasing in 0 .. lds - 1; NULL: the columns 0 .. n_cols - 1; 1 <= n_cols <= 256) are the regressors, taken as they
+ *     are.  No concatenated matrix is built; rows of positions that do not count (w <= 0) are never read, in either input.  Both
+ *     only read the population and Sb, their scratch is the summaries' buffer (the cross pass: n_cols x length(prior) x
+ *     ceil(N / 2048) partial sums), and each synchronises once; a select enqueued ahead and every other state of the context survive
+ *     them.  Refusals come under the prefix "adjust:".
+ *     adjust_cross: S_sx_out[n_cols][length(prior)] (HOST) = T(w (s_j - s_mean[j]) (x_k - x_mean[k])), the rectangular second
+ *       central moments between blob column cols[j] and parameter k; s_mean[n_cols] (HOST: the means of the CHOSEN columns, from
+ *       abcdez_columns_moments) and x_mean[length(prior)] (HOST, from abcdez_posterior_moments) must be finite.               */
+ABCDEZ_API int abcdez_adjust_cross(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                   const double* wns, const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols,
+                                   const double* s_mean, const double* x_mean, double* S_sx_out);
+/*     adjust_apply: Y[N][ldy] (DEVICE, ldy >= length(prior)), row i = x_i - sum_j beta[j][.] (s_i,cols[j] - target[j]) with j
+ *       ascending, one subtraction, one multiplication and one addition per term, for the positions that count; +0.0 in the
+ *       columns 0 .. length(prior) - 1 for the others.  target[n_cols] and beta[n_cols][length(prior)] are HOST arrays and must be
+ *       finite.  Y is a matrix abcdez_columns_* summarise under the same weights.                                          */
+ABCDEZ_API int abcdez_adjust_apply(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                   const double* wns, const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols,
+                                   const double* target, const double* beta, double* Y, int32_t ldy);
+
 /* Test hooks: evaluate the spec arithmetic on the device (fn: 0 log, 1 exp, 2 sincos2pi,
  * 3 rint, 4 floor, 5 sqrt, 6 x/y2, 7 table log, 8 table sincos2pi, 9 sqrt_pn, 10 lgamma,
  * 11 log-density of the context's prior factor (int)y2[i] at x[i], src/abcdez_priors.jl:41-45). */

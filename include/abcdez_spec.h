@@ -987,7 +987,41 @@ ABZ_HD double abz_tree_sum_small(const double* x, int p2) { /* p2 = power of two
  *   histograms (abz_hist_bin, the automatic range over the counting positions, the tallies under / over / NaN / outside2) --
  *   value for value, with the same limits and the same refusals.  The unweighted type-7 quantiles are not part of it.
  *   The posterior predictive summary of a run is this with X = the blobs of the N positions of the current generation, rebuilt
- *   from their stamps (the re-run distance must be the stored one, bit for bit), columns 0 .. n_blob - 1, under Wns. */
+ *   from their stamps (the re-run distance must be the stored one, bit for bit), columns 0 .. n_blob - 1, under Wns.
+ *
+ * REGRESSION ADJUSTMENT (the local-linear ABC adjustment of Beaumont, Zhang and Balding 2002, Genetics 162: the `loclinear` method of
+ * R's abc, `adjust_posterior` of pyABC and ELFI): every accepted particle is corrected for the gap between its simulation and the
+ * observation, theta*_i = theta_i - beta^T (s_i - s_obs).  This text binds the implementations.
+ *   x_ik = push_p of parameter k < d of position i, as above.  s_ij = blob column cols[j], j < c, of position i, TAKEN AS IT IS.
+ *   w_i = Wns_i (1 for every particle of abcdemc); a position COUNTS iff w_i > 0; T = the tile tree over the positions.
+ *   cols is strictly increasing in 0 .. n_blob - 1 (default: all), 1 <= c <= 256.  The target t has c doubles, all finite; its
+ *   default is the simulator's data when they are one number per blob column (n_data == n_blob), restricted to cols; otherwise it
+ *   is required (a blob such as theta^2 + 1 or a pair of residuals has no default).
+ *   W, Q, n_pos, xmean_k, smean_j and S_ss are exactly those of the posterior summaries (of x) and of the column summaries (of the
+ *   blobs).  New: the c x d matrix
+ *     S_sx[j][k] = T(abz_summary_term2(w_i, s_ij, smean_j, x_ik, xmean_k)),
+ *   a position that does not count contributing +0.0, neither of its rows being read.
+ *   Solve (on the host, plain double, no BLAS, no contraction; the same text in every host):
+ *     A = S_ss[cols][cols];  A_jj <- A_jj (1 + ridge), one addition and one multiplication, ridge >= 0 and finite, default 0.
+ *     Cholesky, row by row, j = 0 .. c - 1:  L_jk = (A_jk - sum_{p<k} L_jp L_kp) / L_kk for k < j, then
+ *       r_j = A_jj - sum_{p<j} L_jp L_jp,  L_jj = sqrt(r_j).  Every sum starts at +0.0 and adds its products in ascending p; it is
+ *       subtracted once.
+ *     Refused ("adjust: the simulated data are collinear or constant in column cols[j]: pass `ridge` or fewer `columns`") unless
+ *       r_j is finite and r_j > 2^-40 A_jj.  The threshold is derived, not measured: the rounding of a pivot is bounded by about
+ *       c 2^-52 A_jj <= 2^-44 A_jj at c = 256, and 2^-40 leaves a factor 16.  (A constant column has A_jj = 0, which no ridge lifts.)
+ *     For every parameter k:  z_j = (S_sx[j][k] - sum_{p<j} L_jp z_p) / L_jj, j ascending;
+ *                             beta_jk = (z_j - sum_{p>j} L_pj beta_pk) / L_jj, j descending; sums as above, ascending p.
+ *     A non-finite entry of S_ss[cols][cols], S_sx or t is refused, and so is a non-finite beta.
+ *   Apply, for a position that counts and every k < d:
+ *     acc = +0.0;  for j = 0 .. c - 1 ascending: acc = acc + beta_jk (s_ij - t_j)   one subtraction, one multiplication, one
+ *     addition, no fma;  y_ik = x_ik - acc.
+ *   Row i of Y for a position that does not count is +0.0 in every column, and its inputs are never read.  The order over j is
+ *   fixed, so any mapping of positions and columns to threads gives the same bits.
+ *   The adjusted summaries are the COLUMN SUMMARIES of Y (N x d) under the same weights: no new arithmetic.
+ *   What the adjustment does not do: adjusted values of a discrete parameter are no longer integers; adjusted values may leave the
+ *   prior's support (the method's known caveat; transforms are the user's business); and the regression weights are Wns -- with an
+ *   Epanechnikov ABC kernel those already are the kernel weights of the method, with an indicator kernel the regression is uniform
+ *   over the accepted particles. */
 ABZ_HD uint64_t abz_sample_point(uint64_t seed, uint32_t s, uint32_t draw, uint64_t q, uint64_t r) {
   const uint64_t a = (uint64_t)s * q + ((uint64_t)s < r ? (uint64_t)s : r);
   const uint64_t h = q + ((uint64_t)s < r ? 1u : 0u);

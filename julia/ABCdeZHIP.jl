@@ -636,6 +636,131 @@ function posterior_predictive(e::Engine; packed::Bool=true, cov::Bool=false, cor
         devfree(rows); devfree(X); devfree(redo)
     end
 end
+# ---- regression adjustment (include/abcdez_spec.h "REGRESSION ADJUSTMENT"; library version 670): the local-linear ABC adjustment of
+# Beaumont, Zhang and Balding (2002), theta*_i = theta_i - beta' (s_i - target), on the device.  The blobs are rebuilt as in
+# posterior_predictive, the moments of both halves and the cross moments S_sx are computed there, adjust_solve below (the same text as
+# abcdez_amd/summary.py adjust_solve: row-by-row Cholesky, sums in ascending index from +0.0, plain Float64, no BLAS) gives beta, and
+# the adjusted rows are summarised by the column summaries.  columns: 0-based blob columns, strictly increasing (nothing: all);
+# target: one number per chosen column (the engine keeps no copy of the simulator's data, so it is always given here).  It needs
+# N * (blob_width + d) * 8 bytes of device memory while it runs.  rows = true also returns the d x N adjusted rows.
+function adjust_solve(Sss::Matrix{Float64}, Ssx::Matrix{Float64}, ridge::Float64, names)
+    c = size(Sss, 1); d = size(Ssx, 2)
+    (all(isfinite, Sss) && all(isfinite, Ssx)) || error("adjust: a moment of the simulated data is not finite (a NaN or an infinity in the blobs of a particle that counts)")
+    (ridge >= 0.0 && isfinite(ridge)) || error("adjust: ridge must be finite and not negative")
+    A = copy(Sss); L = zeros(c, c)
+    for j in 1:c
+        A[j, j] = A[j, j] * (1.0 + ridge)
+    end
+    for j in 1:c
+        for k in 1:j-1
+            s = 0.0
+            for p in 1:k-1
+                s = s + L[j, p] * L[k, p]
+            end
+            L[j, k] = (A[j, k] - s) / L[k, k]
+        end
+        s = 0.0
+        for p in 1:j-1
+            s = s + L[j, p] * L[j, p]
+        end
+        r = A[j, j] - s
+        (isfinite(r) && r > 2.0^-40 * A[j, j]) ||
+            error("adjust: the simulated data are collinear or constant in column $(names[j]): pass `ridge` or fewer `columns`")
+        L[j, j] = sqrt(r)
+    end
+    beta = Matrix{Float64}(undef, c, d); z = Vector{Float64}(undef, c)
+    for k in 1:d
+        for j in 1:c
+            s = 0.0
+            for p in 1:j-1
+                s = s + L[j, p] * z[p]
+            end
+            z[j] = (Ssx[j, k] - s) / L[j, j]
+        end
+        for j in c:-1:1
+            s = 0.0
+            for p in j+1:c
+                s = s + L[p, j] * beta[p, k]
+            end
+            beta[j, k] = (z[j] - s) / L[j, j]
+        end
+    end
+    all(isfinite, beta) || error("adjust: a regression coefficient is not finite")
+    return beta
+end
+function posterior_adjusted(e::Engine; target, packed::Bool=true, columns=nothing, ridge::Real=0.0, cov::Bool=true, corrected::Bool=true,
+                            wquantiles=Float64[], rows::Bool=false)
+    ccall((:abcdez_version, LIB), Cint, ()) >= 670 || error("ABCdeZHIP: posterior_adjusted needs libabcdez_hip.so version 670 or later (rebuild the library)")
+    e.nb > 0 || error("adjust: needs a simulator that returns blobs (blobs=True)")
+    m = e.nb; d = e.d
+    cols = columns === nothing ? collect(Int32, 0:m-1) : collect(Int32, columns)
+    c = length(cols)
+    (1 <= c <= 256 && cols[1] >= 0 && cols[c] < m && all(diff(cols) .> 0)) ||
+        error("adjust: columns must be strictly increasing blob columns in 0 .. n_blob - 1, at most 256 of them")
+    t = collect(Float64, target)
+    length(t) == c || error("adjust: target must hold $c number(s), one per chosen blob column")
+    all(isfinite, t) || error("adjust: the target is not finite")
+    wd = Ref(Int32(0)); check(ccall((:abcdez_blob_width, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), e.ctx, wd))
+    lds = Int(wd[])
+    gathered = devalloc(8 * e.N * e.ld); Sb = devalloc(8 * e.N * lds); redo = devalloc(8e.N); Y = devalloc(8 * e.N * d)
+    try
+        if packed
+            check(ccall((:abcdez_packed_gather, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        e.ctx, e.bits[e.bc], e.N, e.slot[1], e.slot[2], gathered))
+        end
+        src = packed ? gathered : e.slot[e.cur]
+        check(ccall((:abcdez_blob_eval, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                    e.ctx, src, e.stamp[e.cur], e.N, Sb, redo))
+        check(ccall((:abcdez_sync, LIB), Cint, (Ptr{Cvoid},), e.ctx))
+        R = Vector{Float64}(undef, e.N); Δ = Vector{Float64}(undef, e.N)
+        d2h(e, R, redo, 8e.N); d2h(e, Δ, e.delta[e.cur], 8e.N)
+        reinterpret(UInt64, R) == reinterpret(UInt64, Δ) || error("blobs: a re-run simulation does not reproduce the stored distance")
+        bits = packed ? e.bits[e.bc] : C_NULL; s0 = packed ? e.slot[1] : e.slot[e.cur]; s1 = packed ? e.slot[2] : C_NULL
+        w = packed ? e.wns : C_NULL
+        W = Ref(0.0); Q = Ref(0.0); npos = Ref(Int64(0))
+        xmean = Vector{Float64}(undef, d)
+        check(ccall((:abcdez_posterior_moments, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Float64}, Ref{Int64}),
+                    e.ctx, bits, e.N, s0, s1, w, 0, xmean, C_NULL, W, Q, npos))
+        sall = Vector{Float64}(undef, m); Sall = Matrix{Float64}(undef, m, m)
+        check(ccall((:abcdez_columns_moments, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Float64}, Ref{Int64}),
+                    e.ctx, Sb, lds, m, w, e.N, 1, sall, Sall, W, Q, npos))
+        smean = sall[cols .+ 1]
+        (all(isfinite, smean) && all(isfinite, xmean)) || error("adjust: a moment of the simulated data is not finite (a NaN or an infinity in the blobs of a particle that counts)")
+        SsxT = Matrix{Float64}(undef, d, c)                 # column-major: [k, j] = the library's [j][k]
+        check(ccall((:abcdez_adjust_cross, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    e.ctx, bits, e.N, s0, s1, w, Sb, lds, cols, c, smean, xmean, SsxT))
+        Ssx = permutedims(SsxT)
+        beta = adjust_solve(Sall[cols .+ 1, cols .+ 1], Ssx, Float64(ridge), cols)
+        betaT = permutedims(beta)                           # [k, j]: the library's row-major [j][k]
+        check(ccall((:abcdez_adjust_apply, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32),
+                    e.ctx, bits, e.N, s0, s1, w, Sb, lds, cols, c, t, betaT, Y, d))
+        mean = Vector{Float64}(undef, d); S = Matrix{Float64}(undef, d, d)
+        check(ccall((:abcdez_columns_moments, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Float64}, Ref{Int64}),
+                    e.ctx, Y, d, d, w, e.N, cov ? 1 : 0, mean, S, W, Q, npos))
+        wprobs = collect(Float64, wquantiles); wq = Matrix{Float64}(undef, length(wprobs), d)     # column-major: [q, k] = the library's [k][q]
+        M = UInt64[0]; nmass = Ref(Int64(0))
+        if !isempty(wprobs)
+            check(ccall((:abcdez_columns_wquantiles, LIB), Cint,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{UInt64}, Ref{Int64}),
+                        e.ctx, Y, d, d, w, e.N, 0, d, wprobs, length(wprobs), wq, M, nmass))
+        end
+        Yh = nothing
+        if rows
+            Yh = Matrix{Float64}(undef, d, e.N); d2h(e, Yh, Y, 8 * e.N * d)
+        end
+        den = corrected ? W[] - Q[] / W[] : W[]
+        return (mean = mean, cov = cov ? S ./ den : nothing, W = W[], ess = W[] * W[] / Q[], n_pos = Int(npos[]), wquantiles = wq,
+                M = isempty(wprobs) ? nothing : M[1], n_mass = isempty(wprobs) ? nothing : Int(nmass[]),
+                beta = beta, columns = Int.(cols), target = t, ridge = Float64(ridge), s_mean = smean, x_mean = xmean, S_sx = Ssx, P = Yh)
+    finally
+        devfree(gathered); devfree(Sb); devfree(redo); devfree(Y)
+    end
+end
 # the drivers' `summary` keyword: true, or a NamedTuple of the options above, e.g. (quantiles = [0.025, 0.975],)
 summary_of(e, summary; packed::Bool) = summary === nothing ? nothing :
     posterior_summary(e; packed = packed, (summary === true ? NamedTuple() : summary)...)
