@@ -4,7 +4,7 @@
  * and the simulated data behind it live.  Two passes relate the two halves of a result that the other posterior calls summarise
  * alone -- the parameter rows x (push_p-cast, from the packed population or abcdemc's row array: sum_row) and the blob rows s
  * (Sb + i lds, rebuilt on the device by abcdez_blob_eval, taken as they are):
- *   cross   S_sx[j][k] = T(w_i ((s_ij - smean_j) (x_ik - xmean_k))), the rectangular twin of sum_second_kernel / col_second_kernel:
+ *   cross   S_sx[j][k] = T(w_i ((s_ij - smean_j) (x_ik - xmean_k))), the rectangular kin of sum_second_kernel:
  *           one block = one tile, thread t owns the positions m*512 + 2t + c; 4 centred blob columns of the thread's 8 rows stay in
  *           registers while the centred parameter columns stream past one at a time (two would spill at three waves per SIMD);
  *           the 4 x d sums of the j-block are collected in LDS, c d partials per tile, the tree levels above the tile by the
@@ -39,34 +39,19 @@ struct AdjBlobs {
   int lds, c;
 };
 
-/* position q < 8 of thread t in the tile at `base` */
-__device__ inline int64_t adj_pos(int64_t base, int q) { return base + (q >> 1) * 512 + 2 * threadIdx.x + (q & 1); }
-/* the weights of the 8 positions of thread t in its tile, 0.0 where the position does not count or lies past N (the rows of those
- * are never read), and bit q of the result = the slot of position q's current row; no row pointers are kept */
-__device__ inline uint32_t adj_owned(const SumPop& p, int64_t base, double (&w)[8]) {
+/* bit q of the result = the slot of the current row of position q of the thread (tile_pos) where w[q] > 0.0: the population's
+ * rows without 8 row pointers in registers */
+__device__ inline uint32_t adj_slots(const SumPop& p, int64_t base, const double (&w)[8]) {
   uint32_t slots = 0;
 #pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int64_t i = adj_pos(base, q);
-    double wv = 0.0;
-    if (i < p.N) wv = p.wns ? p.wns[i] : 1.0;
-    const bool live = wv > 0.0;
-    w[q] = live ? wv : 0.0;
-    if (live && p.bits && packed_bit(p.bits, i)) slots |= 1u << q;
-  }
+  for (int q = 0; q < 8; ++q)
+    if (w[q] > 0.0 && p.bits && packed_bit(p.bits, tile_pos(base, q))) slots |= 1u << q;
   return slots;
 }
 __device__ inline const double* adj_xrow(const SumPop& p, int64_t i, uint32_t slot) {
   return (slot ? p.slot1 : p.slot0) + (size_t)i * (size_t)p.ld;
 }
 __device__ inline const double* adj_srow(const AdjBlobs& b, int64_t i) { return b.Sb + (size_t)i * (size_t)b.lds; }
-/* slot t's eight terms and the wave's 64 slots: the in-tile pairing of tile_sum_kernel; every lane gets the wave's sum */
-__device__ inline double adj_wave_tree(const double (&e)[8]) {
-  double s = ((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7]));
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) s = s + shfl_xor_f64(s, off);
-  return s;
-}
 
 /* ---- cross moments: parts[(j d + k) nt + tile] = tile sum of w (s_j - smean_j) (x_k - xmean_k), j < c, k < d */
 __global__ __launch_bounds__(ABZ_BLOCK, 3) void adj_cross_kernel(const abz_model* __restrict__ M, const SumPop p, const AdjBlobs b,
@@ -77,7 +62,8 @@ __global__ __launch_bounds__(ABZ_BLOCK, 3) void adj_cross_kernel(const abz_model
   const int64_t nt = gridDim.x, tile = blockIdx.x;
   const int d = p.d, c = b.c;
   double w[8];
-  const uint32_t slots = adj_owned(p, tile * ABZ_TILE, w);
+  (void)tile_weights(p, tile * ABZ_TILE, w);
+  const uint32_t slots = adj_slots(p, tile * ABZ_TILE, w);
   for (int jb = 0; jb < c; jb += ADJ_JB) {                       /* block-uniform */
     double cj[ADJ_JB][8];
 #pragma unroll
@@ -85,7 +71,7 @@ __global__ __launch_bounds__(ABZ_BLOCK, 3) void adj_cross_kernel(const abz_model
 #pragma unroll
       for (int a = 0; a < ADJ_JB; ++a) {
         const int j = jb + a;
-        cj[a][q] = (w[q] > 0.0 && j < c) ? adj_srow(b, adj_pos(tile * ABZ_TILE, q))[b.cols[j]] - s_mean[j] : 0.0;
+        cj[a][q] = (w[q] > 0.0 && j < c) ? adj_srow(b, tile_pos(tile * ABZ_TILE, q))[b.cols[j]] - s_mean[j] : 0.0;
       }
     }
     for (int kb = 0; kb < d; kb += ADJ_KC) {
@@ -96,7 +82,7 @@ __global__ __launch_bounds__(ABZ_BLOCK, 3) void adj_cross_kernel(const abz_model
         for (int g = 0; g < ADJ_KC; ++g) {
           const int k = kb + g;
           ck[g][q] = (w[q] > 0.0 && k < d)
-                         ? abz_push_p(&M->prior[k], adj_xrow(p, adj_pos(tile * ABZ_TILE, q), (slots >> q) & 1u)[k]) - x_mean[k]
+                         ? abz_push_p(&M->prior[k], adj_xrow(p, tile_pos(tile * ABZ_TILE, q), (slots >> q) & 1u)[k]) - x_mean[k]
                          : 0.0;
         }
       }
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(ABZ_BLOCK, 3) void adj_cross_kernel(const abz_model
             double e[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) e[q] = w[q] > 0.0 ? w[q] * (cj[a][q] * ck[g][q]) : 0.0;   /* abz_summary_term2 on centred values */
-            const double s = adj_wave_tree(e);
+            const double s = tile_wave_tree(e);
             if ((t & 63) == 0) s_acc[a * d + k][wave] = s;
           }
         }
@@ -137,7 +123,7 @@ __global__ __launch_bounds__(ABZ_BLOCK) void adj_apply_kernel(const abz_model* _
   for (int j = t; j < c; j += ABZ_BLOCK) { s_t[j] = target[j]; s_col[j] = b.cols[j]; }
   const bool inside = i < p.N;
   bool live = false;
-  if (inside) live = (p.wns ? p.wns[i] : 1.0) > 0.0;
+  if (inside) live = sum_weight(p, i) > 0.0;
   const double* srow = nullptr;
   const double* xrow = nullptr;
   if (live) { srow = adj_srow(b, i); xrow = sum_row(p, i); }

@@ -1598,7 +1598,7 @@ int abcdez_posterior_sample(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, co
   return abz_posterior_sample_impl(ctx, p, n, draw, delta, stamp, idx_out, P_out, theta_out, delta_out, stamp_out, M, n_mass);
 }
 
-/* Column summaries (csrc/abz_columns.hip): the three summaries above of a dense per-particle matrix X[N][ldx] -- the simulated
+/* Column summaries (ColView, csrc/abz_summary.h): the three summaries above of a dense per-particle matrix X[N][ldx] -- the simulated
  * data behind the particles, for the posterior predictive check -- instead of the parameter rows.  Like their neighbours they only
  * read, and their scratch is the summaries' buffer. */
 static int columns_view(const char* call, abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,

@@ -16,7 +16,9 @@
  *           past, one LDS histogram per pair (j, k) of the batch; bins2^2 cells a pair, H2_CELLS in all.  A pair that does not fit
  *           (bins2 > 90) is cut into row ranges of b_j, one batch each.
  * Non-empty LDS cells are flushed with global 64-bit integer atomics into zeroed outputs.  The host reads [M, n_mass, error |
- * lo, hi | 1-D cells] and the 2-D cells after ONE synchronisation; no state survives the call.
+ * lo, hi | 1-D cells] and the 2-D cells after ONE synchronisation; no state survives the call.  Only range and bin read values: they
+ * are templates over the value source of abz_summary.h, and the same driver serves a dense per-particle matrix
+ * (abz_columns_histograms_impl).
  */
 #include <string.h>
 
@@ -47,8 +49,8 @@ struct HistBatch { int32_t cj, n, r0, r1; int32_t ck[HB_K]; int32_t pair[HB_K]; 
 
 /* ---- range: krange[2 c + {0, 1}] = (smallest, largest) order key of requested column c over the counting positions, for the
  * columns c0 .. c0 + ncols - 1 of the list */
-__global__ __launch_bounds__(ABZ_BLOCK) void hist_range_kernel(const abz_model* __restrict__ M, const SumPop p,
-                                                              const HistCol* __restrict__ cols, int c0, int ncols,
+template <class S>
+__global__ __launch_bounds__(ABZ_BLOCK) void hist_range_kernel(const S p, const HistCol* __restrict__ cols, int c0, int ncols,
                                                               u64* __restrict__ krange) {
   __shared__ u64 s_kmin[H_RC], s_kmax[H_RC];
   __shared__ int s_col[H_RC];
@@ -63,12 +65,11 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_range_kernel(const abz_model* 
   for (int64_t i = (int64_t)blockIdx.x * ABZ_BLOCK + t; i < p.N; i += (int64_t)gridDim.x * ABZ_BLOCK) {
     if (sum_mass(p, i, b) < 1) continue;
     any = true;
-    const double* row = sum_row(p, i);
+    const double* row = p.row(i);
 #pragma unroll
     for (int c = 0; c < H_RC; ++c) {
       if (c < ncols) {
-        const int col = s_col[c];
-        const u64 key = f64_order_key(abz_push_p(&M->prior[col], row[col]));
+        const u64 key = f64_order_key(p.value(row, s_col[c]));
         if (key < kmin[c]) kmin[c] = key;
         if (key > kmax[c]) kmax[c] = key;
       }
@@ -110,8 +111,8 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_setup_kernel(HistCol* __restri
 
 /* ---- bin: mass[i] for i < Nld (0 beyond N), idx1[c Nld + i] and idx2[c Nld + i] (when idx2) for the counting positions;
  * tot[0] = sum of the low 32 bits of the masses, tot[1] = sum of the high 32 bits, tot[2] = n_mass */
-__global__ __launch_bounds__(ABZ_BLOCK) void hist_bin_kernel(const abz_model* __restrict__ M, const SumPop p,
-                                                            const HistCol* __restrict__ cols, int nc, int bins, int bins2,
+template <class S>
+__global__ __launch_bounds__(ABZ_BLOCK) void hist_bin_kernel(const S p, const HistCol* __restrict__ cols, int nc, int bins, int bins2,
                                                             int64_t Nld, u64* __restrict__ mass, uint16_t* __restrict__ idx1,
                                                             uint8_t* __restrict__ idx2, u64* __restrict__ tot) {
   const int t = threadIdx.x;
@@ -122,10 +123,10 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_bin_kernel(const abz_model* __
     mass[i] = m;
     if (m < 1) continue;
     lo += m & 0xFFFFFFFFull; hi += m >> 32; cnt += 1;
-    const double* row = sum_row(p, i);
+    const double* row = p.row(i);
     for (int c = 0; c < nc; ++c) {
       const HistCol h = cols[c];
-      const double x = abz_push_p(&M->prior[h.col], row[h.col]);
+      const double x = p.value(row, h.col);
       idx1[(size_t)c * (size_t)Nld + (size_t)i] = (uint16_t)abz_hist_bin(x, h.lo, h.hi, h.scale, bins);
       if (idx2) {
         const int32_t b2 = abz_hist_bin(x, h.lo, h.hi, h.scale2, bins2);
@@ -245,9 +246,13 @@ __global__ __launch_bounds__(ABZ_BLOCK) void hist_pair_kernel(const u64* __restr
 }
 
 /* ================================================================ host side */
-int abz_histograms_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const SumHistGather& src, const int32_t* cols, int nc,
-                         int bins, const double* range, const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1,
-                         uint64_t* tallies1, uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
+/* the histograms of a source; `call` names the entry point in the refusals */
+template <class S>
+static int histograms_drive(abcdez_ctx* ctx, const char* call, const S& src, const int32_t* cols, int nc, int bins, const double* range,
+                            const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
+                            uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
+  const int64_t N = src.N;
+  const int d = src.cols();
   /* the blob the host uploads: [ columns | key ranges | batches ] */
   std::vector<int> pos((size_t)d, -1);
   std::vector<HistCol> hc((size_t)nc);
@@ -317,14 +322,16 @@ int abz_histograms_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, co
   if (!range) {
     const int nb = (int)(nb64 < H_RANGE_BLOCKS ? nb64 : H_RANGE_BLOCKS);
     for (int c0 = 0; c0 < nc; c0 += H_RC)
-      src.range(ctx->stream, (unsigned)nb, (const HistCol*)dcols, c0, nc - c0 < H_RC ? nc - c0 : H_RC, krange);
+      hipLaunchKernelGGL(hist_range_kernel<S>, dim3((unsigned)nb), dim3(ABZ_BLOCK), 0, ctx->stream, src, (const HistCol*)dcols, c0,
+                         nc - c0 < H_RC ? nc - c0 : H_RC, krange);
   }
   hipLaunchKernelGGL(hist_setup_kernel, dim3(1), dim3(ABZ_BLOCK), 0, ctx->stream, dcols, nc, range ? 0 : 1, (const u64*)krange, bins,
                      bins2, lohi, hdr);
   {
     const int64_t nbl = (Nld + ABZ_BLOCK - 1) / ABZ_BLOCK;
     const int nb = (int)(nbl < H_BIN_BLOCKS ? nbl : H_BIN_BLOCKS);
-    src.bin(ctx->stream, (unsigned)nb, (const HistCol*)dcols, nc, bins, bins2, Nld, mass, idx1, idx2, hdr);
+    hipLaunchKernelGGL(hist_bin_kernel<S>, dim3((unsigned)nb), dim3(ABZ_BLOCK), 0, ctx->stream, src, (const HistCol*)dcols, nc, bins,
+                       bins2, Nld, mass, idx1, idx2, hdr);
   }
   const int64_t tiles = (Nld + H_TILE - 1) / H_TILE;
   {
@@ -375,22 +382,15 @@ int abz_histograms_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, co
   return 0;
 }
 
-struct PopHistGather : SumHistGather {              /* the population's parameter rows, push_p-cast */
-  const abz_model* M;
-  SumPop p;
-  void range(hipStream_t s, unsigned nb, const HistCol* cols, int c0, int ncols, u64* krange) const override {
-    hipLaunchKernelGGL(hist_range_kernel, dim3(nb), dim3(ABZ_BLOCK), 0, s, M, p, cols, c0, ncols, krange);
-  }
-  void bin(hipStream_t s, unsigned nb, const HistCol* cols, int nc, int bins, int bins2, int64_t Nld, u64* mass, uint16_t* idx1,
-           uint8_t* idx2, u64* tot) const override {
-    hipLaunchKernelGGL(hist_bin_kernel, dim3(nb), dim3(ABZ_BLOCK), 0, s, M, p, cols, nc, bins, bins2, Nld, mass, idx1, idx2, tot);
-  }
-};
 int abz_posterior_histograms_impl(abcdez_ctx* ctx, const SumPop& p, const int32_t* cols, int nc, int bins, const double* range,
                                   const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
                                   uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
-  PopHistGather g;
-  g.M = (const abz_model*)ctx->d_model; g.p = p;
-  return abz_histograms_drive(ctx, "posterior_histograms", p.N, p.d, g, cols, nc, bins, range, pairs, n_pairs, bins2, lo_hi, mass1,
-                              tallies1, mass2, outside2, M_out, n_mass);
+  return histograms_drive(ctx, "posterior_histograms", pop_source(ctx, p), cols, nc, bins, range, pairs, n_pairs, bins2, lo_hi, mass1,
+                          tallies1, mass2, outside2, M_out, n_mass);
+}
+int abz_columns_histograms_impl(abcdez_ctx* ctx, const ColView& v, const int32_t* cols, int nc, int bins, const double* range,
+                                const int32_t* pairs, int n_pairs, int bins2, double* lo_hi, uint64_t* mass1, uint64_t* tallies1,
+                                uint64_t* mass2, uint64_t* outside2, uint64_t* M_out, int64_t* n_mass) {
+  return histograms_drive(ctx, "columns_histograms", v, cols, nc, bins, range, pairs, n_pairs, bins2, lo_hi, mass1, tallies1, mass2,
+                          outside2, M_out, n_mass);
 }

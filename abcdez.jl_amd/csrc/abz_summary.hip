@@ -7,7 +7,9 @@
  * Every sum is the fixed tile tree over the POSITIONS (tile_sum_kernel's pairing inside a tile of 2048, levels 1-2 above it),
  * so the results are bit for bit those of the numpy restatement in abcdez_amd/summary.py.  One block = one tile; thread t owns
  * the positions m*512 + 2t + c of its tile (m < 4, c < 2), reads their rows straight from the packed storage (current slot
- * from the position's bit) and applies push_p per component.
+ * from the position's bit) and applies push_p per component.  The two moment passes are templates over the value source of
+ * abz_summary.h, so the same text summarises any dense per-particle matrix (the column summaries, abz_columns_moments_impl);
+ * the columns per trip below are the population's, a matrix takes 4 and 2.
  *   first-moment pass   columns in blocks of 8 per thread (64 doubles of terms in registers), d + 2 partials per tile
  *   second-moment pass  4 centred columns j of the thread's 8 rows stay in registers while the columns k >= j stream past 4 at
  *                       a time from the rows the block has just pulled into the caches; d (d + 1) / 2 partials per tile, no
@@ -28,92 +30,67 @@
 
 int abz_select_impl(abcdez_ctx*, const double*, const uint8_t*, int64_t, int64_t, double*, double*, int64_t*);
 
-#define ABZ_SUM_CB 8        /* first pass: columns per thread and trip */
-#define ABZ_SUM_JB 4        /* second pass: columns j held per thread */
-#define ABZ_SUM_KC 4        /* second pass: columns k streamed per trip */
-
-/* the 8 positions of thread t in its tile: weight (0.0 where the position does not count or lies past N) and current row
- * (NULL there: never read) */
-__device__ inline int sum_owned(const SumPop& p, int64_t base, double (&w)[8], const double* (&row)[8]) {
-  const int t = threadIdx.x;
-  int c = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const int64_t i = base + (q >> 1) * 512 + 2 * t + (q & 1);
-    double wv = 0.0;
-    if (i < p.N) wv = p.wns ? p.wns[i] : 1.0;
-    const bool live = wv > 0.0;
-    w[q] = live ? wv : 0.0;
-    row[q] = nullptr;
-    if (live) row[q] = sum_row(p, i);
-    c += live;
-  }
-  return c;
-}
-/* slot t's eight terms and the wave's 64 slots: the in-tile pairing of tile_sum_kernel; every lane gets the wave's sum */
-__device__ inline double sum_wave_tree(const double (&e)[8]) {
-  double s = ((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7]));
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) s = s + shfl_xor_f64(s, off);
-  return s;
-}
+#define ABZ_SUM_JB 4        /* second pass: columns j held per thread; the columns per trip are the source's (S::CB, S::KC) */
 
 /* ---- first moments: parts[(k) nt + tile] = tile sum of w x_k (k < d), parts[(d) nt + tile] of w, parts[(d+1) nt + tile] of w w */
-__global__ __launch_bounds__(ABZ_BLOCK) void sum_first_kernel(const abz_model* __restrict__ M, const SumPop p,
-                                                              double* __restrict__ parts, unsigned long long* __restrict__ n_pos) {
-  __shared__ double s_w[ABZ_SUM_CB][4];
+template <class S>
+__global__ __launch_bounds__(ABZ_BLOCK, S::WAVES) void sum_first_kernel(const S src, double* __restrict__ parts,
+                                                                        unsigned long long* __restrict__ n_pos) {
+  __shared__ double s_w[S::CB][4];
   const int t = threadIdx.x, wave = t >> 6;
   const int64_t nt = gridDim.x, tile = blockIdx.x;
+  const int d = src.cols();
   double w[8];
-  const double* row[8];
-  const unsigned long long c = sum_wave_sum_u64((unsigned long long)sum_owned(p, tile * ABZ_TILE, w, row));
+  const unsigned long long c = sum_wave_sum_u64((unsigned long long)tile_weights(src, tile * ABZ_TILE, w));
+  const TileRows<S> row(src, tile * ABZ_TILE, w);
   if ((t & 63) == 0 && c) atomicAdd(n_pos, c);
   {
     double e[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) e[q] = w[q];
-    const double sw = sum_wave_tree(e);
+    const double sw = tile_wave_tree(e);
 #pragma unroll
     for (int q = 0; q < 8; ++q) e[q] = w[q] * w[q];
-    const double sq = sum_wave_tree(e);
+    const double sq = tile_wave_tree(e);
     if ((t & 63) == 0) { s_w[0][wave] = sw; s_w[1][wave] = sq; }
     __syncthreads();
-    if (t < 2) parts[(size_t)(p.d + t) * nt + tile] = (s_w[t][0] + s_w[t][1]) + (s_w[t][2] + s_w[t][3]);
+    if (t < 2) parts[(size_t)(d + t) * nt + tile] = (s_w[t][0] + s_w[t][1]) + (s_w[t][2] + s_w[t][3]);
     __syncthreads();
   }
-  for (int cb = 0; cb < p.d; cb += ABZ_SUM_CB) {                 /* block-uniform */
-    double e[ABZ_SUM_CB][8];
+  for (int cb = 0; cb < d; cb += S::CB) {                        /* block-uniform */
+    double e[S::CB][8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
 #pragma unroll
-      for (int a = 0; a < ABZ_SUM_CB; ++a) {
+      for (int a = 0; a < S::CB; ++a) {
         const int k = cb + a;
         double v = 0.0;
-        if (row[q] && k < p.d) v = abz_summary_term1(w[q], abz_push_p(&M->prior[k], row[q][k]));
+        if (row.live(q) && k < d) v = abz_summary_term1(w[q], src.value(row[q], k));
         e[a][q] = v;
       }
     }
 #pragma unroll
-    for (int a = 0; a < ABZ_SUM_CB; ++a) {
-      const double s = sum_wave_tree(e[a]);
+    for (int a = 0; a < S::CB; ++a) {
+      const double s = tile_wave_tree(e[a]);
       if ((t & 63) == 0) s_w[a][wave] = s;
     }
     __syncthreads();
-    if (t < ABZ_SUM_CB && cb + t < p.d) parts[(size_t)(cb + t) * nt + tile] = (s_w[t][0] + s_w[t][1]) + (s_w[t][2] + s_w[t][3]);
+    if (t < S::CB && cb + t < d) parts[(size_t)(cb + t) * nt + tile] = (s_w[t][0] + s_w[t][1]) + (s_w[t][2] + s_w[t][3]);
     __syncthreads();
   }
 }
 
 /* ---- second central moments: parts[pair(j, k) nt + tile], pair(j, k) = j d - j (j - 1) / 2 + (k - j), j <= k < d */
-__global__ __launch_bounds__(ABZ_BLOCK) void sum_second_kernel(const abz_model* __restrict__ M, const SumPop p,
-                                                               const double* __restrict__ mean, double* __restrict__ parts) {
-  __shared__ double s_acc[ABZ_SUM_JB * ABZ_MAX_D][4];            /* (a, k) -> the four waves' sums */
+template <class S>
+__global__ __launch_bounds__(ABZ_BLOCK, S::WAVES) void sum_second_kernel(const S src, const double* __restrict__ mean,
+                                                                         double* __restrict__ parts) {
+  __shared__ double s_acc[ABZ_SUM_JB * S::MAX_COLS][4];          /* (a, k) -> the four waves' sums */
   const int t = threadIdx.x, wave = t >> 6;
   const int64_t nt = gridDim.x, tile = blockIdx.x;
-  const int d = p.d;
+  const int d = src.cols();
   double w[8];
-  const double* row[8];
-  (void)sum_owned(p, tile * ABZ_TILE, w, row);
+  (void)tile_weights(src, tile * ABZ_TILE, w);
+  const TileRows<S> row(src, tile * ABZ_TILE, w);
   for (int jb = 0; jb < d; jb += ABZ_SUM_JB) {                   /* block-uniform */
     double cj[ABZ_SUM_JB][8];
 #pragma unroll
@@ -121,29 +98,29 @@ __global__ __launch_bounds__(ABZ_BLOCK) void sum_second_kernel(const abz_model* 
 #pragma unroll
       for (int a = 0; a < ABZ_SUM_JB; ++a) {
         const int j = jb + a;
-        cj[a][q] = (row[q] && j < d) ? abz_push_p(&M->prior[j], row[q][j]) - mean[j] : 0.0;
+        cj[a][q] = (row.live(q) && j < d) ? src.value(row[q], j) - mean[j] : 0.0;
       }
     }
-    for (int kb = jb; kb < d; kb += ABZ_SUM_KC) {
-      double ck[ABZ_SUM_KC][8];
+    for (int kb = jb; kb < d; kb += S::KC) {
+      double ck[S::KC][8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
 #pragma unroll
-        for (int b = 0; b < ABZ_SUM_KC; ++b) {
+        for (int b = 0; b < S::KC; ++b) {
           const int k = kb + b;
-          ck[b][q] = (row[q] && k < d) ? abz_push_p(&M->prior[k], row[q][k]) - mean[k] : 0.0;
+          ck[b][q] = (row.live(q) && k < d) ? src.value(row[q], k) - mean[k] : 0.0;
         }
       }
 #pragma unroll
       for (int a = 0; a < ABZ_SUM_JB; ++a) {
 #pragma unroll
-        for (int b = 0; b < ABZ_SUM_KC; ++b) {
+        for (int b = 0; b < S::KC; ++b) {
           const int j = jb + a, k = kb + b;
           if (j <= k && k < d) {                                 /* block-uniform */
             double e[8];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) e[q] = row[q] ? w[q] * (cj[a][q] * ck[b][q]) : 0.0;   /* abz_summary_term2 on centred values */
-            const double s = sum_wave_tree(e);
+            for (int q = 0; q < 8; ++q) e[q] = row.live(q) ? w[q] * (cj[a][q] * ck[b][q]) : 0.0;   /* abz_summary_term2 on centred values */
+            const double s = tile_wave_tree(e);
             if ((t & 63) == 0) s_acc[a * d + k][wave] = s;
           }
         }
@@ -179,7 +156,7 @@ __device__ inline double sum_finish_tile(const double* __restrict__ x, int64_t n
     e[2 * m] = k < n ? x[k] : 0.0;
     e[2 * m + 1] = k + 1 < n ? x[k + 1] : 0.0;
   }
-  const double s = sum_wave_tree(e);
+  const double s = tile_wave_tree(e);
   __syncthreads();                                     /* s_w is reused from tile to tile */
   if ((t & 63) == 0) s_w[t >> 6] = s;
   __syncthreads();
@@ -214,7 +191,7 @@ __global__ __launch_bounds__(ABZ_BLOCK) void sum_column_kernel(const abz_model* 
   const int64_t i = (int64_t)blockIdx.x * ABZ_BLOCK + threadIdx.x;
   bool live = false;
   if (i < p.N) {
-    live = (p.wns ? p.wns[i] : 1.0) > 0.0;
+    live = sum_weight(p, i) > 0.0;
     double v = 0.0;
     if (live) v = abz_push_p(&M->prior[k], sum_row(p, i)[k]);
     col[i] = v;
@@ -257,8 +234,12 @@ int abz_sum_finish(abcdez_ctx* ctx, const double* parts, int64_t n, double* out,
   return 0;
 }
 
-int abz_moments_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const SumMomentsGather& src, int want_second, double* mean,
-                      double* S, double* W, double* Q, int64_t* n_pos) {
+/* the moments of a source; `call` names the entry point in the refusal */
+template <class Src>
+static int moments_drive(abcdez_ctx* ctx, const char* call, const Src& src, int want_second, double* mean, double* S, double* W, double* Q,
+                         int64_t* n_pos) {
+  const int64_t N = src.N;
+  const int d = src.cols();
   const size_t nt = (size_t)((N + ABZ_TILE - 1) / ABZ_TILE);
   const size_t npairs = (size_t)d * (size_t)(d + 1) / 2;
   const size_t ntrees = want_second && npairs > (size_t)d + 2 ? npairs : (size_t)d + 2;
@@ -273,7 +254,7 @@ int abz_moments_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const
   double* parts = (double*)(base + o_parts);
 
   ABZ_HIP_CHECK(hipMemsetAsync(d_npos, 0, 8, ctx->stream));
-  src.first(ctx->stream, (unsigned)nt, parts, d_npos);
+  hipLaunchKernelGGL(sum_first_kernel<Src>, dim3((unsigned)nt), dim3(ABZ_BLOCK), 0, ctx->stream, src, parts, d_npos);
   SumFinishArgs f{parts, (int64_t)nt, res1, d, d};
   hipLaunchKernelGGL(sum_finish_kernel, dim3((unsigned)(d + 2)), dim3(ABZ_BLOCK), 0, ctx->stream, f);
   ABZ_HIP_CHECK(hipGetLastError());
@@ -287,7 +268,7 @@ int abz_moments_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const
   *W = h1[d]; *Q = h1[d + 1]; *n_pos = (int64_t)h_npos;
   if (!want_second) return 0;
 
-  src.second(ctx->stream, (unsigned)nt, (const double*)res1, parts);
+  hipLaunchKernelGGL(sum_second_kernel<Src>, dim3((unsigned)nt), dim3(ABZ_BLOCK), 0, ctx->stream, src, (const double*)res1, parts);
   SumFinishArgs g{parts, (int64_t)nt, res2, 0, 0};
   hipLaunchKernelGGL(sum_finish_kernel, dim3((unsigned)npairs), dim3(ABZ_BLOCK), 0, ctx->stream, g);
   ABZ_HIP_CHECK(hipGetLastError());
@@ -300,21 +281,13 @@ int abz_moments_drive(abcdez_ctx* ctx, const char* call, int64_t N, int d, const
   return 0;
 }
 
-struct PopMomentsGather : SumMomentsGather {       /* the population's parameter rows, push_p-cast */
-  const abz_model* M;
-  SumPop p;
-  void first(hipStream_t s, unsigned nt, double* parts, unsigned long long* n_pos) const override {
-    hipLaunchKernelGGL(sum_first_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, s, M, p, parts, n_pos);
-  }
-  void second(hipStream_t s, unsigned nt, const double* mean, double* parts) const override {
-    hipLaunchKernelGGL(sum_second_kernel, dim3(nt), dim3(ABZ_BLOCK), 0, s, M, p, mean, parts);
-  }
-};
 int abz_posterior_moments_impl(abcdez_ctx* ctx, const SumPop& p, int want_second, double* mean, double* S, double* W, double* Q,
                                int64_t* n_pos) {
-  PopMomentsGather g;
-  g.M = (const abz_model*)ctx->d_model; g.p = p;
-  return abz_moments_drive(ctx, "posterior_moments", p.N, p.d, g, want_second, mean, S, W, Q, n_pos);
+  return moments_drive(ctx, "posterior_moments", pop_source(ctx, p), want_second, mean, S, W, Q, n_pos);
+}
+int abz_columns_moments_impl(abcdez_ctx* ctx, const ColView& v, int want_second, double* mean, double* S, double* W, double* Q,
+                             int64_t* n_pos) {
+  return moments_drive(ctx, "columns_moments", v, want_second, mean, S, W, Q, n_pos);
 }
 
 int abz_posterior_quantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k, const double* probs, int n_probs, double* q_out) {

@@ -15,7 +15,8 @@
  *   close     per slot: smallest mass among the keys equal to the selected one, largest counting key below it
  *   final     the interpolation, into the result array on the device
  * Nothing is read by the host until the very end: one copy of [M, n_mass | results], one synchronisation per call.  The select
- * of the generations (abz_select_impl) is not involved and no state survives the call.
+ * of the generations (abz_select_impl) is not involved and no state survives the call.  Only the gather reads values: it is a
+ * template over the value source of abz_summary.h, and the same driver serves a dense per-particle matrix (abz_columns_wquantiles_impl).
  */
 #include <string.h>
 
@@ -50,10 +51,12 @@ struct WqProbs { double p[WQ_PB]; int n; };
 
 /* ---- gather: keys[c N + i] for the counting positions (others are never read: their mass is 0), mass[i], the totals
  * tot[0] = sum of the low 32 bits of the masses, tot[1] = sum of the high 32 bits, tot[2] = n_mass (first chunk only), and
- * parts[(c nb + block) 3 + {0, 1, 2}] = (smallest key, smallest mass at it, largest key) of the block's positions */
-__global__ __launch_bounds__(ABZ_BLOCK) void wq_gather_kernel(const abz_model* __restrict__ M, const SumPop p, int k_first, int ncols,
-                                                             u64* __restrict__ keys, u64* __restrict__ mass, int first_chunk,
-                                                             u64* __restrict__ parts, u64* __restrict__ tot) {
+ * parts[(c nb + block) 3 + {0, 1, 2}] = (smallest key, smallest mass at it, largest key) of the block's positions; the columns
+ * k_first .. k_first + ncols - 1 of the source */
+template <class S>
+__global__ __launch_bounds__(ABZ_BLOCK) void wq_gather_kernel(const S p, int k_first, int ncols, u64* __restrict__ keys,
+                                                             u64* __restrict__ mass, int first_chunk, u64* __restrict__ parts,
+                                                             u64* __restrict__ tot) {
   __shared__ u64 s_kmin[WQ_CB], s_m1[WQ_CB], s_kmax[WQ_CB];
   const int t = threadIdx.x;
   u64 kmin[WQ_CB], m1[WQ_CB], kmax[WQ_CB];
@@ -67,11 +70,11 @@ __global__ __launch_bounds__(ABZ_BLOCK) void wq_gather_kernel(const abz_model* _
     if (first_chunk) mass[i] = m;
     if (m < 1) continue;
     lo += m & 0xFFFFFFFFull; hi += m >> 32; cnt += 1;
-    const double* row = sum_row(p, i) + k_first;
+    const double* row = p.row(i);
 #pragma unroll
     for (int c = 0; c < WQ_CB; ++c) {
       if (c < ncols) {
-        const u64 key = f64_order_key(abz_push_p(&M->prior[k_first + c], row[c]));
+        const u64 key = f64_order_key(p.value(row, k_first + c));
         keys[(size_t)c * (size_t)p.N + (size_t)i] = key;
         if (key < kmin[c] || (key == kmin[c] && m < m1[c])) { kmin[c] = key; m1[c] = m; }
         if (key > kmax[c]) kmax[c] = key;
@@ -297,8 +300,11 @@ __global__ void wq_final_kernel(const WqState* __restrict__ st, int np, double* 
 }
 
 /* ================================================================ host side */
-int abz_wquantiles_drive(abcdez_ctx* ctx, const char* call, int64_t N, int nk, const SumWqGather& src, const double* probs, int n_probs,
-                         double* q_out, uint64_t* M_out, int64_t* n_mass) {
+/* the columns k0 .. k0 + nk - 1 of a source; `call` names the entry point in the refusals */
+template <class S>
+static int wquantiles_drive(abcdez_ctx* ctx, const char* call, const S& src, int k0, int nk, const double* probs, int n_probs,
+                            double* q_out, uint64_t* M_out, int64_t* n_mass) {
+  const int64_t N = src.N;
   size_t fit = WQ_KEY_BYTES / ((size_t)N * 8);                         /* columns whose keys fit the chunk */
   fit = fit < 1 ? 1 : fit > WQ_CB ? WQ_CB : fit;
   const int ncc = (int)fit < nk ? (int)fit : nk;
@@ -325,7 +331,8 @@ int abz_wquantiles_drive(abcdez_ctx* ctx, const char* call, int64_t N, int nk, c
   ABZ_HIP_CHECK(hipMemsetAsync(base, 0, o_parts, ctx->stream));        /* totals, results, states, histograms */
   for (int c0 = 0; c0 < nk; c0 += ncc) {
     const int nc = nk - c0 < ncc ? nk - c0 : ncc;
-    src.gather(ctx->stream, (unsigned)nb, c0, nc, keys, mass, c0 == 0 ? 1 : 0, parts, tot);
+    hipLaunchKernelGGL(wq_gather_kernel<S>, dim3((unsigned)nb), dim3(ABZ_BLOCK), 0, ctx->stream, src, k0 + c0, nc, keys, mass,
+                       c0 == 0 ? 1 : 0, parts, tot);
     for (int q0 = 0; q0 < n_probs; q0 += WQ_PB) {
       WqProbs pr{};
       pr.n = n_probs - q0 < WQ_PB ? n_probs - q0 : WQ_PB;
@@ -352,17 +359,11 @@ int abz_wquantiles_drive(abcdez_ctx* ctx, const char* call, int64_t N, int nk, c
   return 0;
 }
 
-struct PopWqGather : SumWqGather {                  /* the population's parameter rows from column k0 on, push_p-cast */
-  const abz_model* M;
-  SumPop p;
-  int k0;
-  void gather(hipStream_t s, unsigned nb, int c0, int ncols, u64* keys, u64* mass, int first_chunk, u64* parts, u64* tot) const override {
-    hipLaunchKernelGGL(wq_gather_kernel, dim3(nb), dim3(ABZ_BLOCK), 0, s, M, p, k0 + c0, ncols, keys, mass, first_chunk, parts, tot);
-  }
-};
 int abz_posterior_wquantiles_impl(abcdez_ctx* ctx, const SumPop& p, int k0, int nk, const double* probs, int n_probs, double* q_out,
                                   uint64_t* M_out, int64_t* n_mass) {
-  PopWqGather g;
-  g.M = (const abz_model*)ctx->d_model; g.p = p; g.k0 = k0;
-  return abz_wquantiles_drive(ctx, "posterior_wquantiles", p.N, nk, g, probs, n_probs, q_out, M_out, n_mass);
+  return wquantiles_drive(ctx, "posterior_wquantiles", pop_source(ctx, p), k0, nk, probs, n_probs, q_out, M_out, n_mass);
+}
+int abz_columns_wquantiles_impl(abcdez_ctx* ctx, const ColView& v, int k0, int nk, const double* probs, int n_probs, double* q_out,
+                                uint64_t* M_out, int64_t* n_mass) {
+  return wquantiles_drive(ctx, "columns_wquantiles", v, k0, nk, probs, n_probs, q_out, M_out, n_mass);
 }

@@ -1539,8 +1539,8 @@ class PopulationEngine:
 
         On the HIP engine the blobs of all N positions are rebuilt on the device from the stamps of the current generation, exactly
         as :meth:`result` does it (the re-run's distance is checked bit for bit against the stored one), summarised there under the
-        population's weights (csrc/abz_columns.hip; bit for bit :func:`abcdez_amd.summary.predictive_reference` of the downloaded
-        ``blobs`` and ``Wns``) and freed: only the summary travels to the host.  It needs N x blob_width x 8 bytes of device memory
+        population's weights (the dense-matrix source of csrc/abz_summary.h; bit for bit
+        :func:`abcdez_amd.summary.predictive_reference` of the downloaded ``blobs`` and ``Wns``) and freed: only the summary travels to the host.  It needs N x blob_width x 8 bytes of device memory
         for the matrix while it runs, and changes nothing a continued run depends on.  Engines without the device call compute the
         restatement on ``result()["blobs"]``.  A simulator without blobs is refused."""
         from . import summary as _summary

@@ -2,7 +2,8 @@
 tests/test_columns_kernel_resources.py.  The cross pass holds 4 centred blob columns of 8 rows per thread (64 registers) next to the
 streamed parameter column and collects 4 x 256 x 4 partial sums in LDS; the apply pass keeps 8 accumulators and stages 256 x 8
 coefficients in LDS.  An array that ended up in scratch memory would go out to HBM and back per position, invisible in every
-parity test.  The occupancy is compared with the shipped twin of the cross pass, col_second_kernel of the same tree."""
+parity test.  The occupancy is compared with the shipped kin of the cross pass: the second-moment pass over a dense matrix
+(sum_second_kernel<ColView>, csrc/abz_summary.hip) of the same tree."""
 import pytest
 
 from test_kernel_resources import HIPCC, resource_table
@@ -16,7 +17,7 @@ def test_the_adjust_kernels_run_without_scratch_and_keep_their_twins_occupancy()
     assert len(rows) == len(KERNELS), sorted(rows)
     for k in KERNELS:
         assert any(k in name for name in rows), (k, sorted(rows))
-    twin = [r for name, r in resource_table("abz_columns.hip").items() if "col_second_kernel" in name]
+    twin = [r for name, r in resource_table("abz_summary.hip").items() if "sum_second_kernel" in name and "ColView" in name]
     assert len(twin) == 1
     floor = int(twin[0]["Occupancy [waves/SIMD]"])
     assert floor >= 1

@@ -1,6 +1,6 @@
-"""Column summaries / posterior predictive on the device (csrc/abz_columns.hip: abcdez_columns_moments / _wquantiles /
-_histograms, PopulationEngine.posterior_predictive) against abcdez_amd.summary.summary_reference / predictive_reference of data
-that reached the host through the existing routes (the uploaded matrix itself, or ``r.blobs`` and ``r.Wns`` of the downloaded
+"""Column summaries / posterior predictive on the device (the dense-matrix source of csrc/abz_summary.h: abcdez_columns_moments /
+_wquantiles / _histograms, PopulationEngine.posterior_predictive) against abcdez_amd.summary.summary_reference /
+predictive_reference of data that reached the host through the existing routes (the uploaded matrix itself, or ``r.blobs`` and ``r.Wns`` of the downloaded
 result) -- BIT FOR BIT: float64 fields as uint64, integer fields exactly.  Crafted matrices go to the C entry points as plain device
 pointers (the technique of tests/test_gpu_posterior_summary_edges.py): rows of weightless positions and the padding columns beyond m
 hold NaN, so that one missing guard in a kernel poisons a sum."""

@@ -4,6 +4,7 @@ Round 5 lost 15 % of the d = 32 sweep's fabric traffic budget to ONE 16-byte sta
 memory (a conditionally written array: 16 bytes per lane out to HBM and back; profiles/HISTORY.md) -- invisible in every parity test.
 This pins what the DESIGN.md numbers rest on: no scratch, no spills, an LDS footprint that leaves room for six workgroups per CU,
 registers for five waves per SIMD."""
+import functools
 import os
 import re
 import shutil
@@ -16,6 +17,7 @@ CSRC = os.path.join(ROOT, "abcdez.jl_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
 
 
+@functools.lru_cache(maxsize=None)
 def resource_table(src):
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Ibuild",
            "-I../../include", "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
