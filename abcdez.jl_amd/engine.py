@@ -32,7 +32,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -46,6 +46,52 @@ PACKED_ALIGN = 64        # sub-ranges of the packed prefix start / end at multip
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+class PopValues(NamedTuple):
+    """Value source of the posterior summaries, host side of ``PopSource`` (csrc/abz_summary.h): the push_p-cast rows of the live
+    population.  ``bits`` None: ``slot0`` is a classic row array; ``wns`` None: unit weights."""
+    bits: Optional[torch.Tensor]
+    slot0: torch.Tensor
+    slot1: Optional[torch.Tensor]
+    wns: Optional[torch.Tensor]
+    N: int
+    width: int          # spec.d
+
+    prefix = "abcdez_posterior_"
+    who = "posterior"                                                   # names the source in host-side ValueErrors
+    since = {"moments": 620, "wquantiles": 630, "histograms": 640}      # library version that added each call
+
+    @property
+    def lead(self):
+        """the C arguments between the context and the call's own"""
+        return _ptr(self.bits), self.N, _ptr(self.slot0), _ptr(self.slot1), _ptr(self.wns)
+
+
+class ColValues(NamedTuple):
+    """Value source of the posterior summaries, host side of ``ColView`` (csrc/abz_summary.h): the first ``m`` columns of a dense
+    device matrix X[N][ldx] under the weights ``wns`` (None: unit weights)."""
+    X: torch.Tensor
+    ldx: int
+    m: int
+    wns: Optional[torch.Tensor]
+
+    prefix = "abcdez_columns_"
+    who = "columns"
+    since = {"moments": 660, "wquantiles": 660, "histograms": 660}
+
+    @classmethod
+    def of(cls, X, wns, m=None):
+        ldx, m = HipOps._columns_view(X, m)
+        return cls(X, ldx, m, wns)
+
+    @property
+    def width(self):
+        return self.m
+
+    @property
+    def lead(self):
+        return _ptr(self.X), self.ldx, self.m, _ptr(self.wns), int(self.X.shape[0])
 
 
 def pg_host_transport(pg, with_allreduce: bool = False):
@@ -464,17 +510,56 @@ class HipOps:
                                    "rebuild it (`make -C abcdez.jl_amd/csrc`)")
         return fn
 
+    # The three summaries are marshalled ONCE, over a value source (PopValues / ColValues above: the host side of
+    # csrc/abz_summary.h); the posterior_* / columns_* methods below name the source and keep their own signatures.
+    def summary_moments(self, src, want_second=True):
+        """(mean[width], S[width, width] or None, W, Q, n_pos) of the value source ``src`` (abcdez_{posterior,columns}_moments)"""
+        mm = max(src.width, 1)
+        mean = np.empty(mm, dtype=np.float64)
+        S = np.empty((mm, mm), dtype=np.float64) if want_second else None
+        W, Q, n_pos = C.c_double(), C.c_double(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn(src.prefix + "moments", src.since["moments"])(
+            self.ctx, *src.lead, 1 if want_second else 0, mean.ctypes.data, S.ctypes.data if want_second else None, C.byref(W),
+            C.byref(Q), C.byref(n_pos)))
+        return mean, S, W.value, Q.value, n_pos.value
+
+    def summary_wquantiles(self, src, probs, k0=0, nk=None):
+        """(q[nk, len(probs)], M, n_mass) of the columns k0 .. k0 + nk - 1 of ``src`` (abcdez_{posterior,columns}_wquantiles)"""
+        nk = src.width - int(k0) if nk is None else int(nk)
+        p = np.ascontiguousarray(probs, dtype=np.float64)
+        q = np.empty((max(nk, 0), p.size), dtype=np.float64)
+        M, n_mass = C.c_uint64(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn(src.prefix + "wquantiles", src.since["wquantiles"])(
+            self.ctx, *src.lead, int(k0), nk, p.ctypes.data, int(p.size), q.ctypes.data, C.byref(M), C.byref(n_mass)))
+        return q, M.value, n_mass.value
+
+    def summary_histograms(self, src, columns=None, bins=64, range=None, pairs=(), bins2=None):
+        """the tuple of :meth:`posterior_histograms` for the value source ``src`` (abcdez_{posterior,columns}_histograms)"""
+        cols = np.arange(max(src.width, 0), dtype=np.int32) if columns is None else np.ascontiguousarray(columns, dtype=np.int32).reshape(-1)
+        nc = int(cols.size)
+        bins, bins2 = int(bins), int(bins if bins2 is None else bins2)
+        rg = None if range is None else np.ascontiguousarray(range, dtype=np.float64).reshape(-1)
+        if rg is not None and rg.size != 2 * nc:
+            raise ValueError(f"{src.who}_histograms: range must hold (lo, hi) per requested column")
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        npairs = int(pr.shape[0])
+        lo_hi = np.empty((nc, 2), dtype=np.float64)
+        mass1 = np.zeros((nc, max(bins, 0)), dtype=np.uint64)
+        tallies1 = np.zeros((nc, 3), dtype=np.uint64)
+        b2 = max(bins2, 0) if npairs else 0
+        mass2 = np.zeros((npairs, b2, b2), dtype=np.uint64)
+        outside2 = np.zeros(npairs, dtype=np.uint64)
+        M, n_mass = C.c_uint64(), C.c_int64()
+        _lib.check(self.lib, self._summary_fn(src.prefix + "histograms", src.since["histograms"])(
+            self.ctx, *src.lead, cols.ctypes.data, nc, bins, None if rg is None else rg.ctypes.data,
+            pr.ctypes.data if npairs else None, npairs, bins2, lo_hi.ctypes.data, mass1.ctypes.data, tallies1.ctypes.data,
+            mass2.ctypes.data if npairs else None, outside2.ctypes.data if npairs else None, C.byref(M), C.byref(n_mass)))
+        return lo_hi, mass1, tallies1, mass2, outside2, M.value, n_mass.value
+
     def posterior_moments(self, bits, slot0, slot1, wns, N, want_second=True):
         """(mean[d], S[d, d] or None, W, Q, n_pos) of the population on the device; bits None: slot0 is a classic row array,
         wns None: unit weights (include/abcdez_hip.h, abcdez_posterior_moments)"""
-        d = self.spec.d
-        mean = np.empty(d, dtype=np.float64)
-        S = np.empty((d, d), dtype=np.float64) if want_second else None
-        W, Q, n_pos = C.c_double(), C.c_double(), C.c_int64()
-        _lib.check(self.lib, self._summary_fn("abcdez_posterior_moments")(
-            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), 1 if want_second else 0, mean.ctypes.data,
-            S.ctypes.data if want_second else None, C.byref(W), C.byref(Q), C.byref(n_pos)))
-        return mean, S, W.value, Q.value, n_pos.value
+        return self.summary_moments(PopValues(bits, slot0, slot1, wns, N, self.spec.d), want_second)
 
     def posterior_quantiles(self, bits, slot0, slot1, wns, N, k, probs):
         """type-7 quantiles at ``probs`` of parameter k over the particles with a positive weight (abcdez_posterior_quantiles)"""
@@ -487,41 +572,14 @@ class HipOps:
     def posterior_wquantiles(self, bits, slot0, slot1, wns, N, probs, k0=0, nk=None):
         """(q[nk, len(probs)], M, n_mass): weighted quantiles at ``probs`` of the parameters k0 .. k0 + nk - 1 (default: all from k0)
         over the integer masses of the resampler, one library call and one read-back (abcdez_posterior_wquantiles)"""
-        nk = self.spec.d - int(k0) if nk is None else int(nk)
-        p = np.ascontiguousarray(probs, dtype=np.float64)
-        q = np.empty((max(nk, 0), p.size), dtype=np.float64)
-        M, n_mass = C.c_uint64(), C.c_int64()
-        _lib.check(self.lib, self._summary_fn("abcdez_posterior_wquantiles", 630)(
-            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), int(k0), nk, p.ctypes.data, int(p.size), q.ctypes.data,
-            C.byref(M), C.byref(n_mass)))
-        return q, M.value, n_mass.value
+        return self.summary_wquantiles(PopValues(bits, slot0, slot1, wns, N, self.spec.d), probs, k0, nk)
 
     def posterior_histograms(self, bits, slot0, slot1, wns, N, columns=None, bins=64, range=None, pairs=(), bins2=None):
         """(lo_hi[n_cols, 2], mass1[n_cols, bins], tallies1[n_cols, 3], mass2[n_pairs, bins2, bins2], outside2[n_pairs], M, n_mass):
         marginal and pairwise histograms over the integer masses of the resampler, one library call (abcdez_posterior_histograms).
         ``columns``: strictly increasing parameter indices (None: all); ``range``: n_cols x 2 or None for the automatic range;
         ``pairs``: (j, k) parameter indices"""
-        cols = np.arange(self.spec.d, dtype=np.int32) if columns is None else np.ascontiguousarray(columns, dtype=np.int32).reshape(-1)
-        nc = int(cols.size)
-        bins, bins2 = int(bins), int(bins if bins2 is None else bins2)
-        rg = None if range is None else np.ascontiguousarray(range, dtype=np.float64).reshape(-1)
-        if rg is not None and rg.size != 2 * nc:
-            raise ValueError("posterior_histograms: range must hold (lo, hi) per requested column")
-        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        npairs = int(pr.shape[0])
-        lo_hi = np.empty((nc, 2), dtype=np.float64)
-        mass1 = np.zeros((nc, max(bins, 0)), dtype=np.uint64)
-        tallies1 = np.zeros((nc, 3), dtype=np.uint64)
-        b2 = max(bins2, 0) if npairs else 0
-        mass2 = np.zeros((npairs, b2, b2), dtype=np.uint64)
-        outside2 = np.zeros(npairs, dtype=np.uint64)
-        M, n_mass = C.c_uint64(), C.c_int64()
-        _lib.check(self.lib, self._summary_fn("abcdez_posterior_histograms", 640)(
-            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), cols.ctypes.data, nc, bins,
-            None if rg is None else rg.ctypes.data, pr.ctypes.data if npairs else None, npairs, bins2, lo_hi.ctypes.data,
-            mass1.ctypes.data, tallies1.ctypes.data, mass2.ctypes.data if npairs else None, outside2.ctypes.data if npairs else None,
-            C.byref(M), C.byref(n_mass)))
-        return lo_hi, mass1, tallies1, mass2, outside2, M.value, n_mass.value
+        return self.summary_histograms(PopValues(bits, slot0, slot1, wns, N, self.spec.d), columns, bins, range, pairs, bins2)
 
     def posterior_sample(self, bits, slot0, slot1, wns, N, n, draw=0, delta=None, stamp=None, want_theta=False):
         """(index[n] int32, P[n, d], theta[n, ld] or None, delta[n] or None, stamp[n] or None, M, n_mass): n equally weighted draws
@@ -553,55 +611,18 @@ class HipOps:
     def columns_moments(self, X, wns, m=None, want_second=True):
         """(mean[m], S[m, m] or None, W, Q, n_pos) of the first m columns of the device matrix X[N][ldx] under the weights wns
         (None: unit weights), abcdez_columns_moments"""
-        ldx, m = self._columns_view(X, m)
-        mm = max(m, 1)
-        mean = np.empty(mm, dtype=np.float64)
-        S = np.empty((mm, mm), dtype=np.float64) if want_second else None
-        W, Q, n_pos = C.c_double(), C.c_double(), C.c_int64()
-        _lib.check(self.lib, self._summary_fn("abcdez_columns_moments", 660)(
-            self.ctx, _ptr(X), ldx, m, _ptr(wns), int(X.shape[0]), 1 if want_second else 0, mean.ctypes.data,
-            S.ctypes.data if want_second else None, C.byref(W), C.byref(Q), C.byref(n_pos)))
-        return mean, S, W.value, Q.value, n_pos.value
+        return self.summary_moments(ColValues.of(X, wns, m), want_second)
 
     def columns_wquantiles(self, X, wns, probs, m=None, k0=0, nk=None):
         """(q[nk, len(probs)], M, n_mass): weighted quantiles at ``probs`` of the columns k0 .. k0 + nk - 1 (default: all from k0
         up to m) of X over the integer masses of the resampler, one library call and one read-back (abcdez_columns_wquantiles)"""
-        ldx, m = self._columns_view(X, m)
-        nk = m - int(k0) if nk is None else int(nk)
-        p = np.ascontiguousarray(probs, dtype=np.float64)
-        q = np.empty((max(nk, 0), p.size), dtype=np.float64)
-        M, n_mass = C.c_uint64(), C.c_int64()
-        _lib.check(self.lib, self._summary_fn("abcdez_columns_wquantiles", 660)(
-            self.ctx, _ptr(X), ldx, m, _ptr(wns), int(X.shape[0]), int(k0), nk, p.ctypes.data, int(p.size), q.ctypes.data,
-            C.byref(M), C.byref(n_mass)))
-        return q, M.value, n_mass.value
+        return self.summary_wquantiles(ColValues.of(X, wns, m), probs, k0, nk)
 
     def columns_histograms(self, X, wns, m=None, columns=None, bins=64, range=None, pairs=(), bins2=None):
         """(lo_hi[n_cols, 2], mass1[n_cols, bins], tallies1[n_cols, 3], mass2[n_pairs, bins2, bins2], outside2[n_pairs], M, n_mass):
         marginal and pairwise histograms of columns of X over the integer masses of the resampler, one library call
         (abcdez_columns_histograms); the arguments are those of :meth:`posterior_histograms` with column indices in 0 .. m - 1"""
-        ldx, m = self._columns_view(X, m)
-        cols = np.arange(max(m, 0), dtype=np.int32) if columns is None else np.ascontiguousarray(columns, dtype=np.int32).reshape(-1)
-        nc = int(cols.size)
-        bins, bins2 = int(bins), int(bins if bins2 is None else bins2)
-        rg = None if range is None else np.ascontiguousarray(range, dtype=np.float64).reshape(-1)
-        if rg is not None and rg.size != 2 * nc:
-            raise ValueError("columns_histograms: range must hold (lo, hi) per requested column")
-        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        npairs = int(pr.shape[0])
-        lo_hi = np.empty((nc, 2), dtype=np.float64)
-        mass1 = np.zeros((nc, max(bins, 0)), dtype=np.uint64)
-        tallies1 = np.zeros((nc, 3), dtype=np.uint64)
-        b2 = max(bins2, 0) if npairs else 0
-        mass2 = np.zeros((npairs, b2, b2), dtype=np.uint64)
-        outside2 = np.zeros(npairs, dtype=np.uint64)
-        M, n_mass = C.c_uint64(), C.c_int64()
-        _lib.check(self.lib, self._summary_fn("abcdez_columns_histograms", 660)(
-            self.ctx, _ptr(X), ldx, m, _ptr(wns), int(X.shape[0]), cols.ctypes.data, nc, bins,
-            None if rg is None else rg.ctypes.data, pr.ctypes.data if npairs else None, npairs, bins2, lo_hi.ctypes.data,
-            mass1.ctypes.data, tallies1.ctypes.data, mass2.ctypes.data if npairs else None, outside2.ctypes.data if npairs else None,
-            C.byref(M), C.byref(n_mass)))
-        return lo_hi, mass1, tallies1, mass2, outside2, M.value, n_mass.value
+        return self.summary_histograms(ColValues.of(X, wns, m), columns, bins, range, pairs, bins2)
 
     # ---- regression adjustment: the two device passes between the parameter rows and the blobs (include/abcdez_hip.h, R3) ----
     @staticmethod
@@ -1433,6 +1454,59 @@ class PopulationEngine:
             return self.bits[self.bc], self.buf[0][0], self.buf[1][0], self.wns
         return None, self.buf[self.cur][0], None, None
 
+    def _weights(self):
+        """the population's weights on the device; abcdemc has none (None: every particle counts once)"""
+        return self.wns if self.packed else None
+
+    @staticmethod
+    def _probabilities(who, *groups):
+        groups = tuple(tuple(float(p) for p in g) for g in groups)
+        if any(not 0.0 <= p <= 1.0 for g in groups for p in g):
+            raise ValueError(f"{who}: p must be in [0, 1]")
+        return groups
+
+    @staticmethod
+    def _hist_options(hist, width):
+        """the checked ``hist`` option (summary.hist_options), or None when no histogram is asked for"""
+        from . import summary as _summary
+
+        return None if hist is None or hist is False else _summary.hist_options(hist, width)
+
+    def _rebuild_blobs(self, theta, stamp, delta):
+        """The simulated data behind the rows ``theta``, rebuilt on the device from their stamps: a matrix len(theta) x blob_width.
+        The re-run's distance must be the stored one ``delta``, bit for bit."""
+        out = torch.zeros((theta.shape[0], self.ops.blob_width()), dtype=torch.float64, device=self.device)
+        redo = torch.empty_like(delta)
+        self.ops.blob_eval(theta, stamp, out, redo)
+        if not torch.equal(redo.view(torch.int64), delta.view(torch.int64)):
+            raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
+        return out
+
+    def _summarise(self, src, cov, corrected, probs, wprobs, hist, hist_opts=None):
+        """The tail the three posterior calls share, over a value source of the ops (PopValues / ColValues): moments, the unweighted
+        quantiles ``probs`` (population source only), the weighted ones, the histograms -> the record of summary.make_summary.
+        ``hist_opts``: the checked ``hist`` where the caller had to check it before its own device work."""
+        from . import summary as _summary
+
+        mean, S, W, Q, n_pos = self.ops.summary_moments(src, want_second=cov)
+        qs = np.empty((len(probs), src.width))
+        if probs:
+            for k in range(src.width):
+                qs[:, k] = self.ops.posterior_quantiles(*src[:5], k, probs)
+        wq = M = n_mass = None
+        if wprobs:
+            q, M, n_mass = self.ops.summary_wquantiles(src, wprobs)
+            wq = np.ascontiguousarray(q.T)
+        h = None
+        if hist_opts is None:
+            hist_opts = self._hist_options(hist, src.width)
+        if hist_opts is not None:
+            cols, bins, rng_, pairs, bins2 = hist_opts
+            lo_hi, mass1, tallies1, mass2, outside2, M, n_mass = self.ops.summary_histograms(
+                src, columns=cols, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
+            h = _summary.make_hist(cols, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
+        return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass, h)
+
     def posterior_summary(self, cov: bool = True, corrected: bool = True, quantiles=(), wquantiles=(), hist=None):
         """Posterior summaries of the population where it lives (include/abcdez_spec.h, "posterior summaries"): a record with
         ``mean`` (d), ``cov`` (d x d; None without ``cov``), ``quantiles`` (len(quantiles) x d marginal type-7 quantiles over the
@@ -1455,32 +1529,13 @@ class PopulationEngine:
         or one per column; None: the smallest and largest counting value of each column.  ``bins2`` defaults to min(bins, 128)."""
         from . import summary as _summary
 
-        probs = tuple(float(p) for p in quantiles)
-        wprobs = tuple(float(p) for p in wquantiles)
-        if any(not 0.0 <= p <= 1.0 for p in probs + wprobs):
-            raise ValueError("summary: p must be in [0, 1]")
+        probs, wprobs = self._probabilities("summary", quantiles, wquantiles)
         if not hasattr(self.ops, "posterior_moments"):
             res = self.result()
             return _summary.summary_reference(res["P"], res["Wns"] if self.packed else None, cov=cov, corrected=corrected,
                                               quantiles=probs, wquantiles=wprobs, hist=hist)
         self._stream()
-        pop = self._live_population()
-        mean, S, W, Q, n_pos = self.ops.posterior_moments(*pop, self.N, want_second=cov)
-        qs = np.empty((len(probs), self.spec.d))
-        if probs:
-            for k in range(self.spec.d):
-                qs[:, k] = self.ops.posterior_quantiles(*pop, self.N, k, probs)
-        wq = M = n_mass = None
-        if wprobs:
-            q, M, n_mass = self.ops.posterior_wquantiles(*pop, self.N, wprobs)
-            wq = np.ascontiguousarray(q.T)
-        h = None
-        if hist is not None and hist is not False:
-            cols, bins, rng_, pairs, bins2 = _summary.hist_options(hist, self.spec.d)
-            lo_hi, mass1, tallies1, mass2, outside2, M, n_mass = self.ops.posterior_histograms(
-                *pop, self.N, columns=cols, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
-            h = _summary.make_hist(cols, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
-        return _summary.make_summary(mean, S, W, Q, n_pos, qs, probs, corrected, wq, wprobs, M, n_mass, h)
+        return self._summarise(PopValues(*self._live_population(), self.N, self.spec.d), cov, corrected, probs, wprobs, hist)
 
     def posterior_sample(self, n: int, draw: int = 0, blobs=None):
         """``n`` equally weighted draws from the weighted population (include/abcdez_spec.h, "POSTERIOR SAMPLE"): what the
@@ -1513,14 +1568,7 @@ class PopulationEngine:
             *pop, self.N, n, draw, delta=self.buf[self.cur][2], stamp=self.stamp[self.cur] if want_blobs else None, want_theta=want_blobs)
         send = [idx, P, dl]
         if want_blobs:
-            # the simulated data behind the n gathered distances, rebuilt from their stamps; as in result() the re-run's distance
-            # must be the gathered one, bit for bit
-            out = torch.zeros((n, self.ops.blob_width()), dtype=torch.float64, device=self.device)
-            redo = torch.empty_like(dl)
-            self.ops.blob_eval(th, st, out, redo)
-            if not torch.equal(redo.view(torch.int64), dl.view(torch.int64)):
-                raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
-            send.append(out[:, :self.spec.n_blob])
+            send.append(self._rebuild_blobs(th, st, dl)[:, :self.spec.n_blob])      # of the n gathered rows only
         got = self._to_host(send)
         Ph = got[1][:, 0] if squeeze else got[1]
         bl = None
@@ -1545,40 +1593,19 @@ class PopulationEngine:
         restatement on ``result()["blobs"]``.  A simulator without blobs is refused."""
         from . import summary as _summary
 
-        wprobs = tuple(float(p) for p in wquantiles)
-        if any(not 0.0 <= p <= 1.0 for p in wprobs):
-            raise ValueError("predictive: p must be in [0, 1]")
+        wprobs, = self._probabilities("predictive", wquantiles)
         if not self.blob_on:
             raise ValueError(_summary.PREDICTIVE_NEEDS_BLOBS)
         nb = self.spec.n_blob
-        if hist is not None and hist is not False:
-            hist_opts = _summary.hist_options(hist, nb)
+        hist_opts = self._hist_options(hist, nb)
         if not hasattr(self.ops, "columns_moments"):
             res = self.result()
             return _summary.predictive_reference(res["blobs"], res["Wns"] if self.packed else None, cov=cov, corrected=corrected,
                                                  wquantiles=wprobs, hist=hist)
         self._stream()
         th, _, dl = self.state
-        X = torch.zeros((self.N, self.ops.blob_width()), dtype=torch.float64, device=self.device)
-        redo = torch.empty_like(dl)
-        self.ops.blob_eval(th, self.stamp[self.cur], X, redo)
-        if not torch.equal(redo.view(torch.int64), dl.view(torch.int64)):
-            raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
-        del redo
-        wns = self.wns if self.packed else None
-        mean, S, W, Q, n_pos = self.ops.columns_moments(X, wns, m=nb, want_second=cov)
-        wq = M = n_mass = None
-        if wprobs:
-            q, M, n_mass = self.ops.columns_wquantiles(X, wns, wprobs, m=nb)
-            wq = np.ascontiguousarray(q.T)
-        h = None
-        if hist is not None and hist is not False:
-            cols, bins, rng_, pairs, bins2 = hist_opts
-            lo_hi, mass1, tallies1, mass2, outside2, M, n_mass = self.ops.columns_histograms(
-                X, wns, m=nb, columns=cols, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
-            h = _summary.make_hist(cols, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
-        del X
-        return _summary.make_summary(mean, S, W, Q, n_pos, np.empty((0, nb)), (), corrected, wq, wprobs, M, n_mass, h)
+        X = self._rebuild_blobs(th, self.stamp[self.cur], dl)
+        return self._summarise(ColValues.of(X, self._weights(), nb), cov, corrected, (), wprobs, hist, hist_opts)
 
     def posterior_adjusted(self, columns=None, target=None, ridge: float = 0.0, cov: bool = True, corrected: bool = True, wquantiles=(),
                            hist=None, rows: bool = False):
@@ -1605,32 +1632,23 @@ class PopulationEngine:
         calls compute the restatement on ``result()``.  A simulator without blobs is refused."""
         from . import summary as _summary
 
-        wprobs = tuple(float(p) for p in wquantiles)
-        if any(not 0.0 <= p <= 1.0 for p in wprobs):
-            raise ValueError("adjust: p must be in [0, 1]")
+        wprobs, = self._probabilities("adjust", wquantiles)
         if not self.blob_on:
             raise ValueError(_summary.ADJUST_NEEDS_BLOBS)
         nb, d = self.spec.n_blob, self.spec.d
         cols = _summary.adjust_columns(columns, nb)
         t = _summary.adjust_target(target, cols, nb, tuple(self.spec.sim.data()))
         ridge = _summary.adjust_ridge(ridge)
-        want_hist = hist is not None and hist is not False
-        if want_hist:
-            hist_opts = _summary.hist_options(hist, d)
+        hist_opts = self._hist_options(hist, d)
         if not hasattr(self.ops, "adjust_cross"):
             res = self.result()
             return _summary.adjust_reference(res["P"], res["blobs"], res["Wns"] if self.packed else None, target=t, columns=cols,
                                              ridge=ridge, cov=cov, corrected=corrected, wquantiles=wprobs, hist=hist, rows=rows)
         self._stream()
         th, _, dl = self.state
-        Sb = torch.zeros((self.N, self.ops.blob_width()), dtype=torch.float64, device=self.device)
-        redo = torch.empty_like(dl)
-        self.ops.blob_eval(th, self.stamp[self.cur], Sb, redo)
-        if not torch.equal(redo.view(torch.int64), dl.view(torch.int64)):
-            raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
-        del redo
+        Sb = self._rebuild_blobs(th, self.stamp[self.cur], dl)
         pop = self._live_population()
-        wns = self.wns if self.packed else None
+        wns = self._weights()
         x_mean = self.ops.posterior_moments(*pop, self.N, want_second=False)[0]
         s_all, S_all = self.ops.columns_moments(Sb, wns, m=nb, want_second=True)[:2]
         s_mean = s_all[cols]
@@ -1639,20 +1657,9 @@ class PopulationEngine:
         beta = _summary.adjust_solve(S_all[np.ix_(cols, cols)], S_sx, ridge, cols)
         Y = self.ops.adjust_apply(*pop, self.N, Sb, cols, t, beta)
         del Sb
-        mean, S, W, Q, n_pos = self.ops.columns_moments(Y, wns, m=d, want_second=cov)
-        wq = M = n_mass = None
-        if wprobs:
-            q, M, n_mass = self.ops.columns_wquantiles(Y, wns, wprobs, m=d)
-            wq = np.ascontiguousarray(q.T)
-        h = None
-        if want_hist:
-            hc, bins, rng_, pairs, bins2 = hist_opts
-            lo_hi, mass1, tallies1, mass2, outside2, M, n_mass = self.ops.columns_histograms(
-                Y, wns, m=d, columns=hc, bins=bins, range=rng_, pairs=pairs, bins2=bins2)
-            h = _summary.make_hist(hc, bins, lo_hi, mass1, tallies1, pairs, bins2, mass2, outside2, M, n_mass)
+        rec = self._summarise(ColValues.of(Y, wns, d), cov, corrected, (), wprobs, hist, hist_opts)
         Ph = self._to_host([Y])[0] if rows else None
         del Y
-        rec = _summary.make_summary(mean, S, W, Q, n_pos, np.empty((0, d)), (), corrected, wq, wprobs, M, n_mass, h)
         return _summary.make_adjusted(rec, beta, cols, t, ridge, s_mean, x_mean, S_sx, Ph)
 
     def _to_host(self, tensors):
@@ -1684,15 +1691,7 @@ class PopulationEngine:
         blobs = None
         blob_dev = None
         if self.blob_on:
-            # rebuild the simulated data behind every particle's distance from its stamp; the re-run's distance
-            # must be the stored one, bit for bit
-            nb = self.spec.n_blob
-            out = torch.zeros((self.N, self.ops.blob_width()), dtype=torch.float64, device=self.device)
-            redo = torch.empty_like(dl)
-            self.ops.blob_eval(th, self.stamp[self.cur], out, redo)
-            if not torch.equal(redo.view(torch.int64), dl.view(torch.int64)):
-                raise RuntimeError("blobs: a re-run simulation does not reproduce the stored distance")
-            blob_dev = out[:, :nb]
+            blob_dev = self._rebuild_blobs(th, self.stamp[self.cur], dl)[:, :self.spec.n_blob]
         send = [th[:, :d], lp, dl, self.wns, self.alive] + ([pushed[:, :d]] if discrete else []) + ([blob_dev] if blob_dev is not None else [])
         got = self._to_host(send)
         theta, logpi, Cc, Wns, alive = got[:5]

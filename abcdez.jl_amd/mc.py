@@ -12,7 +12,7 @@ import math
 
 from .model import ModelSpec
 from .priors import prior_length
-from .smc import Result, _adjust_options, _check, _make_engine, _predictive_options, _sample_options, _summary_options, load_checkpoint
+from .smc import Result, _check, _make_engine, _posterior_options, _posterior_records, load_checkpoint
 
 log = logging.getLogger("abcdez_amd")
 
@@ -33,10 +33,7 @@ def abcdemc(prior, dist, ϵ_target, varexternal=None, *,
     ``adjust=True | dict(columns=, target=, ridge=, cov=, corrected=, wquantiles=, hist=, rows=)``: as in :func:`abcdesmc`,
     ``r.adjusted`` (unit weights: an ordinary least-squares adjustment over all particles).
     """
-    smp_opts = _sample_options(sample)
-    prd_opts = _predictive_options(predictive)
-    adj_opts = _adjust_options(adjust)
-    sum_opts = _summary_options(summary, download, sample, prd_opts, adj_opts)
+    post_opts = _posterior_options(summary, download, sample, predictive, adjust)
     α = 0.0                                                   # mc:107
     _check(0.0 <= ϵ_target, "ϵ_target must be non-negative")  # mc:108
     _check(5 <= nparticles, "nparticles must be at least 5")  # mc:109
@@ -48,12 +45,11 @@ def abcdemc(prior, dist, ϵ_target, varexternal=None, *,
     # serialises with every other blocking stream of the process (and could not be captured when graph replay -- optional,
     # off by default: measured slower -- is switched on)
     with (eng.run_scope() if hasattr(eng, "run_scope") else contextlib.nullcontext()):
-        return _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, resume, α, parallel, sum_opts, download,
-                            smp_opts, prd_opts, adj_opts)
+        return _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, resume, α, parallel, download, post_opts)
 
 
-def _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, resume, α, parallel=False, sum_opts=None,
-                 download=True, smp_opts=None, prd_opts=None, adj_opts=None):
+def _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, resume, α, parallel=False, download=True,
+                 post_opts=(None, None, None, None)):
     if verbose:                                               # mc:113-114
         log.info("Running abcdemc! with executor %s (%d rank(s))", type(getattr(eng, "ops", eng)).__name__, getattr(eng, "world", 1))
         log.info("Running abcdemc! with ϵ_target=%s nparticles=%d generations=%d α=%s rng=%s parallel=%s", ϵ_target, nparticles,
@@ -105,22 +101,7 @@ def _abcdemc_run(eng, spec, prior, ϵ_target, nparticles, generations, verbose, 
         log.info("End: completion=%s converged=%s nsim=%d range_ϵ=%s", complete, conv, nsims, (ϵ_l, ϵ_h))
     res = eng.result() if download else {"P": None, "C": None}             # mc:166
     out = Result(P=res["P"], C=res["C"], reached_ϵ=conv, blobs=res.get("blobs"))
-    if sum_opts is not None:
-        from .summary import engine_summary
-
-        out.summary = engine_summary(eng, **sum_opts)
-    if smp_opts is not None:
-        from .summary import engine_sample
-
-        out.sample = engine_sample(eng, **smp_opts)
-    if prd_opts is not None:
-        from .summary import engine_predictive
-
-        out.predictive = engine_predictive(eng, **prd_opts)
-    if adj_opts is not None:
-        from .summary import engine_adjusted
-
-        out.adjusted = engine_adjusted(eng, **adj_opts)
+    _posterior_records(out, eng, *post_opts)
     out.reached_eps = conv
     out.nsims, out.updates, out.complete = nsims, generations * nparticles, complete
     out.engine = eng

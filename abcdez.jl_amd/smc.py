@@ -102,45 +102,34 @@ def _check(cond: bool, msg: str) -> None:
         raise ValueError(msg)  # the reference raises ErrorException via error(...)
 
 
-def _summary_options(summary, download, sample=None, predictive=None, adjust=None):
-    """the drivers' ``summary`` / ``download`` keywords -> options of posterior_summary, or None (``sample``, ``predictive``,
-    ``adjust``: the drivers' keywords of those names -- with any of them the result is not empty either)"""
+def _posterior_options(summary, download, sample, predictive, adjust):
+    """the drivers' ``summary`` / ``download`` / ``sample`` / ``predictive`` / ``adjust`` keywords -> the keywords of the engine's
+    posterior_summary, posterior_sample, posterior_predictive and posterior_adjusted, each None when not asked for (``sample``:
+    None; the others: None or False).  Without any of them ``download=False`` is refused: the result would be empty."""
+    from . import summary as S
+
+    smp = None if sample is None else S.sample_options(sample)
+    prd = None if predictive is None or predictive is False else S.predictive_options(predictive)
+    adj = None if adjust is None or adjust is False else S.adjust_options(adjust)
     if summary is None or summary is False:
-        _check(bool(download) or sample is not None or predictive is not None or adjust is not None,
+        _check(bool(download) or sample is not None or prd is not None or adj is not None,
                "download=False needs summary: the result would be empty")
-        return None
-    from .summary import summary_options
-
-    return summary_options(summary)
+        return None, smp, prd, adj
+    return S.summary_options(summary), smp, prd, adj
 
 
-def _sample_options(sample):
-    """the drivers' ``sample`` keyword (an integer n, or a dict of n / draw / blobs) -> keywords of posterior_sample, or None"""
-    if sample is None:
-        return None
-    from .summary import sample_options
+def _posterior_records(out, eng, sum_opts, smp_opts, prd_opts, adj_opts):
+    """fill ``out.summary`` / ``.sample`` / ``.predictive`` / ``.adjusted`` of a driver's result: the ones that were asked for"""
+    from . import summary as S
 
-    return sample_options(sample)
-
-
-def _predictive_options(predictive):
-    """the drivers' ``predictive`` keyword (True, or a dict of cov / corrected / wquantiles / hist) -> keywords of
-    posterior_predictive, or None"""
-    if predictive is None or predictive is False:
-        return None
-    from .summary import predictive_options
-
-    return predictive_options(predictive)
-
-
-def _adjust_options(adjust):
-    """the drivers' ``adjust`` keyword (True, or a dict of columns / target / ridge / cov / corrected / wquantiles / hist / rows) ->
-    keywords of posterior_adjusted, or None"""
-    if adjust is None or adjust is False:
-        return None
-    from .summary import adjust_options
-
-    return adjust_options(adjust)
+    if sum_opts is not None:
+        out.summary = S.engine_summary(eng, **sum_opts)
+    if smp_opts is not None:
+        out.sample = S.engine_sample(eng, **smp_opts)
+    if prd_opts is not None:
+        out.predictive = S.engine_predictive(eng, **prd_opts)
+    if adj_opts is not None:
+        out.adjusted = S.engine_adjusted(eng, **adj_opts)
 
 
 def _make_engine(spec: ModelSpec, nparticles: int, engine, process_group, storage: str = "packed"):
@@ -200,10 +189,7 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     simulation and the observation, theta - beta^T (s - target), and summarised where the population lives.  A run may then stop
     at a larger ϵ_target for the same accuracy.  It needs a simulator with blobs and goes with ``download=False``.
     """
-    smp_opts = _sample_options(sample)
-    prd_opts = _predictive_options(predictive)
-    adj_opts = _adjust_options(adjust)
-    sum_opts = _summary_options(summary, download, sample, prd_opts, adj_opts)
+    post_opts = _posterior_options(summary, download, sample, predictive, adjust)
     # ---- initialisation / validation: src/abcdez_smc.jl:223-235
     _check(0.0 <= α < 1.0, "α must be in 0 <= α < 1")
     _check(0.0 <= δess <= 1.0, "δess must be in 0 <= δess <= 1")
@@ -320,22 +306,7 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
 
     res = eng.result() if download else {"P": None, "Wns": None, "C": None}     # P is push_p-cast, smc:382
     out = Result(P=res["P"], Wns=res["Wns"], C=res["C"], ϵ=ϵ, logZ=logZ, blobs=res.get("blobs"))
-    if sum_opts is not None:
-        from .summary import engine_summary
-
-        out.summary = engine_summary(eng, **sum_opts)
-    if smp_opts is not None:
-        from .summary import engine_sample
-
-        out.sample = engine_sample(eng, **smp_opts)
-    if prd_opts is not None:
-        from .summary import engine_predictive
-
-        out.predictive = engine_predictive(eng, **prd_opts)
-    if adj_opts is not None:
-        from .summary import engine_adjusted
-
-        out.adjusted = engine_adjusted(eng, **adj_opts)
+    _posterior_records(out, eng, *post_opts)
     out.eps = ϵ
     out.iters, out.nsims, out.updates = iters, nsims, updates
     out.engine = eng

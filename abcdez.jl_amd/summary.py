@@ -68,6 +68,32 @@ def cov_denominator(W: float, Q: float, corrected: bool) -> float:
     return W - Q / W if corrected else W
 
 
+def _as_matrix(v):
+    """float64 view of per-particle values with a vector lifted to one column: (N,) -> (N, 1)"""
+    X = np.asarray(v, dtype=np.float64)
+    return X[:, None] if X.ndim == 1 else X
+
+
+def _options(who: str, value, allowed) -> dict:
+    """a driver keyword that is True (the defaults) or a dict of the options ``allowed`` -> a copy of the dict"""
+    if value is True:
+        return {}
+    if isinstance(value, dict):
+        bad = set(value) - set(allowed)
+        if bad:
+            raise ValueError(f"{who}: unknown option(s) {sorted(bad)} ({', '.join(allowed)})")
+        return dict(value)
+    raise ValueError(f"{who} must be None, True or a dict of the options {', '.join(allowed)}")
+
+
+def engine_call(eng, method: str, fallback, **opts):
+    """``eng.<method>(**opts)`` for a PopulationEngine; any other engine object: ``fallback(eng.result(), **opts)``, the numpy
+    restatement on its downloaded result"""
+    if hasattr(eng, method):
+        return getattr(eng, method)(**opts)
+    return fallback(eng.result(), **opts)
+
+
 def make_summary(mean, S, W, Q, n_pos, quantiles, probs, corrected=True, wquantiles=None, wprobs=(), M=None, n_mass=None, hist=None):
     """the record ``posterior_summary`` returns, from what the library (or the restatement below) computes"""
     W, Q = float(W), float(Q)
@@ -277,9 +303,7 @@ def hist_reference(X, w, bins=64, range=None, columns=None, pairs=None, bins2=No
     """The histograms of include/abcdez_spec.h ("posterior summaries", histograms) of the population X (N x d) with the weights w
     (None: every position has the mass 2^b), literally: Python-integer masses, abz_hist_bin, integer sums.  Returns the record
     of :func:`make_hist`; refuses like the library."""
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim == 1:
-        X = X[:, None]
+    X = _as_matrix(X)
     N, d = X.shape
     cols, bins, rng_, pairs, bins2 = hist_options(dict(bins=bins, range=range, columns=columns, pairs=pairs, bins2=bins2), d)
     masses, M, n_mass = integer_masses(w, N)
@@ -326,9 +350,7 @@ def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquan
     (len(quantiles) x d), ``W``, ``Q``, ``ess = W^2 / Q``, ``n_pos``, and for ``wquantiles`` the weighted quantiles ``wquantiles``
     (len(wquantiles) x d) with the total integer mass ``M`` and ``n_mass`` (both None when none are asked for), and for ``hist``
     (the options of :func:`hist_reference`) the record ``hist`` of the marginal and pairwise histograms (None otherwise)."""
-    X = np.asarray(P, dtype=np.float64)
-    if X.ndim == 1:
-        X = X[:, None]
+    X = _as_matrix(P)
     N, d = X.shape
     w = np.ones(N) if Wns is None else np.asarray(Wns, dtype=np.float64)
     if w.shape != (N,):
@@ -382,6 +404,7 @@ def summary_reference(P, Wns=None, cov=True, corrected=True, quantiles=(), wquan
 RNG_SAMPLE = 10                 # ABZ_RNG_SAMPLE
 SAMPLE_MAX_N = (1 << 31) - 1    # ABZ_SAMPLE_MAX_N
 SAMPLE_OPTIONS = ("n", "draw", "blobs")
+SUMMARY_OPTIONS = ("cov", "corrected", "quantiles", "wquantiles", "hist")
 _MASK32 = 0xFFFFFFFF
 
 
@@ -471,36 +494,24 @@ def make_sample(P, index, C, blobs, M, n_mass, n, draw):
 
 def engine_sample(eng, n, draw=0, blobs=None):
     """``eng.posterior_sample(n, draw, blobs)`` for a PopulationEngine; any other engine object: the restatement on its result"""
-    if hasattr(eng, "posterior_sample"):
-        return eng.posterior_sample(n, draw=draw, blobs=blobs)
-    res = eng.result()
-    seed = eng.spec.seed
-    index, M, n_mass = sample_reference(res["P"], res.get("Wns"), n, seed, draw)
-    rb = res.get("blobs")
-    if blobs and rb is None:
-        raise ValueError("sample: blobs=True needs a simulator that returns blobs")
-    return make_sample(res["P"][index], index, res["C"][index], None if (rb is None or blobs is False) else rb[index], M, n_mass, n,
-                       draw)
+    def restated(res, n, draw, blobs):
+        index, M, n_mass = sample_reference(res["P"], res.get("Wns"), n, eng.spec.seed, draw)
+        rb = res.get("blobs")
+        if blobs and rb is None:
+            raise ValueError("sample: blobs=True needs a simulator that returns blobs")
+        return make_sample(res["P"][index], index, res["C"][index], None if (rb is None or blobs is False) else rb[index], M, n_mass,
+                           n, draw)
+    return engine_call(eng, "posterior_sample", restated, n=n, draw=draw, blobs=blobs)
 
 
 def summary_options(summary) -> dict:
     """the ``summary=`` keyword of the drivers: True, or a dict of cov / corrected / quantiles / wquantiles / hist"""
-    if summary is True:
-        return {}
-    if isinstance(summary, dict):
-        bad = set(summary) - {"cov", "corrected", "quantiles", "wquantiles", "hist"}
-        if bad:
-            raise ValueError(f"summary: unknown option(s) {sorted(bad)} (cov, corrected, quantiles, wquantiles, hist)")
-        return dict(summary)
-    raise ValueError("summary must be None, True or a dict of the options cov, corrected, quantiles, wquantiles, hist")
+    return _options("summary", summary, SUMMARY_OPTIONS)
 
 
 def engine_summary(eng, **opts):
     """``eng.posterior_summary(**opts)`` for a PopulationEngine; any other engine object: the restatement on its result"""
-    if hasattr(eng, "posterior_summary"):
-        return eng.posterior_summary(**opts)
-    res = eng.result()
-    return summary_reference(res["P"], res.get("Wns"), **opts)
+    return engine_call(eng, "posterior_summary", lambda res, **o: summary_reference(res["P"], res.get("Wns"), **o), **opts)
 
 
 # ------------------------------------------------------------------ posterior predictive (include/abcdez_spec.h, "column summaries")
@@ -511,14 +522,7 @@ PREDICTIVE_NEEDS_BLOBS = "predictive: needs a simulator that returns blobs (blob
 def predictive_options(predictive) -> dict:
     """the ``predictive=`` keyword of the drivers: True, or a dict of cov / corrected / wquantiles / hist -> the keywords of
     posterior_predictive"""
-    if predictive is True:
-        return {}
-    if isinstance(predictive, dict):
-        bad = set(predictive) - set(PREDICTIVE_OPTIONS)
-        if bad:
-            raise ValueError(f"predictive: unknown option(s) {sorted(bad)} (cov, corrected, wquantiles, hist)")
-        return dict(predictive)
-    raise ValueError("predictive must be None, True or a dict of the options cov, corrected, wquantiles, hist")
+    return _options("predictive", predictive, PREDICTIVE_OPTIONS)
 
 
 def predictive_reference(blobs, Wns=None, cov=False, corrected=True, wquantiles=(), hist=None):
@@ -527,9 +531,7 @@ def predictive_reference(blobs, Wns=None, cov=False, corrected=True, wquantiles=
     values are taken as they are; rows of particles without weight may hold anything.  ``quantiles`` of the record is empty."""
     if blobs is None:
         raise ValueError(PREDICTIVE_NEEDS_BLOBS)
-    X = np.asarray(blobs, dtype=np.float64)
-    if X.ndim == 1:
-        X = X[:, None]
+    X = _as_matrix(blobs)
     if X.ndim != 2:
         raise ValueError("predictive: blobs must be one row of numbers per particle")
     return summary_reference(X, Wns, cov=cov, corrected=corrected, quantiles=(), wquantiles=wquantiles, hist=hist)
@@ -537,12 +539,7 @@ def predictive_reference(blobs, Wns=None, cov=False, corrected=True, wquantiles=
 
 def engine_predictive(eng, **opts):
     """``eng.posterior_predictive(**opts)`` for a PopulationEngine; any other engine object: the restatement on its result"""
-    if hasattr(eng, "posterior_predictive"):
-        return eng.posterior_predictive(**opts)
-    res = eng.result()
-    if res.get("blobs") is None:
-        raise ValueError(PREDICTIVE_NEEDS_BLOBS)
-    return predictive_reference(res["blobs"], res.get("Wns"), **opts)
+    return engine_call(eng, "posterior_predictive", lambda res, **o: predictive_reference(res.get("blobs"), res.get("Wns"), **o), **opts)
 
 
 # ------------------------------------------------------------------ regression adjustment (include/abcdez_spec.h, "REGRESSION ADJUSTMENT")
@@ -555,14 +552,7 @@ ADJUST_PIVOT = 2.0 ** -40       # a pivot must exceed this fraction of its diago
 def adjust_options(adjust) -> dict:
     """the ``adjust=`` keyword of the drivers: True, or a dict of columns / target / ridge / cov / corrected / wquantiles / hist /
     rows -> the keywords of posterior_adjusted"""
-    if adjust is True:
-        return {}
-    if isinstance(adjust, dict):
-        bad = set(adjust) - set(ADJUST_OPTIONS)
-        if bad:
-            raise ValueError(f"adjust: unknown option(s) {sorted(bad)} (columns, target, ridge, cov, corrected, wquantiles, hist, rows)")
-        return dict(adjust)
-    raise ValueError("adjust must be None, True or a dict of the options columns, target, ridge, cov, corrected, wquantiles, hist, rows")
+    return _options("adjust", adjust, ADJUST_OPTIONS)
 
 
 def adjust_columns(columns, n_blob: int):
@@ -698,12 +688,7 @@ def adjust_reference(P, blobs, Wns=None, target=None, columns=None, ridge=0.0, c
     weight may hold anything.  Returns the record of :func:`make_adjusted`."""
     if blobs is None:
         raise ValueError(ADJUST_NEEDS_BLOBS)
-    X = np.asarray(P, dtype=np.float64)
-    if X.ndim == 1:
-        X = X[:, None]
-    B = np.asarray(blobs, dtype=np.float64)
-    if B.ndim == 1:
-        B = B[:, None]
+    X, B = _as_matrix(P), _as_matrix(blobs)
     if X.ndim != 2 or B.ndim != 2 or B.shape[0] != X.shape[0]:
         raise ValueError("adjust: P and blobs must hold one row per particle")
     N, d = X.shape
@@ -733,9 +718,8 @@ def adjust_reference(P, blobs, Wns=None, target=None, columns=None, ridge=0.0, c
 
 def engine_adjusted(eng, **opts):
     """``eng.posterior_adjusted(**opts)`` for a PopulationEngine; any other engine object: the restatement on its result"""
-    if hasattr(eng, "posterior_adjusted"):
-        return eng.posterior_adjusted(**opts)
-    res = eng.result()
-    if res.get("blobs") is None:
-        raise ValueError(ADJUST_NEEDS_BLOBS)
-    return adjust_reference(res["P"], res["blobs"], res.get("Wns"), data=tuple(eng.spec.sim.data()), **opts)
+    def restated(res, **o):
+        if res.get("blobs") is None:
+            raise ValueError(ADJUST_NEEDS_BLOBS)
+        return adjust_reference(res["P"], res["blobs"], res.get("Wns"), data=tuple(eng.spec.sim.data()), **o)
+    return engine_call(eng, "posterior_adjusted", restated, **opts)

@@ -13,7 +13,8 @@ import torch
 import abcdez_amd as A
 from abcdez_amd import _lib
 from abcdez_amd.engine import HipOps, PopulationEngine
-from abcdez_amd.summary import make_hist, make_summary, predictive_reference, summary_reference
+from abcdez_amd.summary import (adjust_reference, make_hist, make_sample, make_summary, predictive_reference, sample_reference,
+                                summary_reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -241,6 +242,45 @@ def test_driver_keyword_and_download_false():
     assert_same_record(bare.predictive, predictive_reference(r.blobs, r.Wns, wquantiles=(0.025, 0.5, 0.975)), "download=False")
     with pytest.raises(ValueError, match=r"predictive: needs a simulator that returns blobs \(blobs=True\)"):
         A.abcdesmc(prior, A.LotkaVolterraRK4(LV_OBS, dt=0.05, steps_per_obs=10), 0.0, None, predictive=True, **kw)
+
+
+# ------------------------------------------------------------------------------------------ all four keywords in one driver call
+ALL = dict(cov=True, wquantiles=PROBS, hist=dict(bins=7))
+DRAWS = dict(n=257, draw=3)
+
+
+def all_keywords_run(driver, N, engine=None, **kw):
+    """One driver call with the download and ``summary``, ``sample``, ``predictive`` and ``adjust`` together (the path on which the
+    four posterior calls share their tail and their blob rebuild): every record is the restatement of the downloaded result, bit
+    for bit.  Normal1D with blobs: P and blobs are vectors.  Returns the driver's result."""
+    from test_gpu_posterior_adjust import assert_same_adjusted
+
+    sim = A.Normal1D(1.5, 1.0, blobs=True)
+    r = driver(A.Normal(0.0, 2.0), sim, kw.pop("target"), None, nparticles=N, verbose=False, rng=5, engine=engine, summary=ALL,
+               sample=DRAWS, predictive=ALL, adjust=dict(ALL, rows=True), **kw)
+    Wns = vars(r).get("Wns")                             # abcdemc: no weights
+    assert r.P.shape == r.C.shape == r.blobs.shape == (N,)
+    assert_same_record(r.summary, summary_reference(r.P, Wns, **ALL), "summary")
+    index, M, n_mass = sample_reference(r.P, Wns, DRAWS["n"], 5, DRAWS["draw"], rounds=r.engine.ops.stream_version()[1])
+    ref = make_sample(r.P[index], index, r.C[index], r.blobs[index], M, n_mass, **DRAWS)
+    assert r.sample.index.dtype == np.int64 and np.array_equal(r.sample.index, ref.index)
+    assert (r.sample.M, r.sample.n_mass, r.sample.n, r.sample.draw) == (ref.M, ref.n_mass, ref.n, ref.draw)
+    for f in ("P", "C", "blobs"):
+        assert getattr(r.sample, f).shape == (DRAWS["n"],) and np.array_equal(bits(getattr(r.sample, f)), bits(getattr(ref, f))), f
+    assert_same_record(r.predictive, predictive_reference(r.blobs, Wns, **ALL), "predictive")
+    assert_same_adjusted(r.adjusted, adjust_reference(r.P, r.blobs, Wns, data=tuple(sim.data()), rows=True, **ALL), "adjust")
+    return r
+
+
+def test_all_four_keywords_in_one_call_packed_storage():
+    """2049 particles: one tile of 2048 and one row"""
+    r = all_keywords_run(A.abcdesmc, 2049, target=0.0, ABCk=A.Epa0toeps, max_iters=3)
+    assert type(r.engine.ops) is HipOps and r.iters == 3 and (r.Wns == 0).any()
+
+
+def test_all_four_keywords_in_one_call_classic_storage():
+    r = all_keywords_run(A.abcdemc, 2049, target=0.5, generations=6)
+    assert type(r.engine.ops) is HipOps and r.summary.n_pos == 2049
 
 
 # ------------------------------------------------------------------------------------------ continuation

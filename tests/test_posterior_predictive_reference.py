@@ -110,6 +110,17 @@ def test_driver_keyword_on_the_cpu_engine(oracle):
     assert np.array_equal(bits(m.predictive.wquantiles), bits(ref.wquantiles))
 
 
+def test_all_four_keywords_in_one_call_on_the_cpu_engine(oracle):
+    """the download with ``summary``, ``sample``, ``predictive`` and ``adjust`` in one driver call: on the CPU test engine every
+    one of the four engine methods takes its fallback, the restatement of ``result()``"""
+    from test_gpu_posterior_predictive import all_keywords_run
+
+    r = all_keywords_run(A.abcdesmc, 600, engine=oracle.oracle_engine, target=0.0, ABCk=A.Epa0toeps, max_iters=3)
+    assert r.iters == 3 and (r.Wns == 0).any() and np.unique(r.Wns[r.Wns > 0]).size > 1
+    m = all_keywords_run(A.abcdemc, 600, engine=oracle.oracle_engine, target=0.5, generations=6)
+    assert m.summary.n_pos == 600 and m.adjusted.W == 600.0
+
+
 def test_refused_without_blobs(oracle):
     prior = A.Factored(A.Uniform(-2, 2), A.Uniform(0, 4))
     kw = dict(nparticles=200, verbose=False, rng=9, engine=oracle.oracle_engine, max_iters=2)

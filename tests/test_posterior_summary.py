@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import abcdez_amd as A
+from abcdez_amd import summary as S
 from abcdez_amd.summary import order_keys, summary_reference, tile_tree_sum
 
 U = 2.0 ** -53
@@ -301,3 +302,145 @@ def test_drivers_summary_and_download_keywords(oracle):
     assert abs(m.summary.mean[0] - m.P.mean()) <= 64 * U * np.abs(m.P).sum() / 200
     with pytest.raises(ValueError, match="download=False needs summary"):
         A.abcdemc(PRIOR, SIM, 0.3, None, download=False, **mkw)
+
+
+# ------------------------------------------------------------------------------------------ refusals, character for character
+def bare_ops(d=3):
+    """a HipOps that never loaded the library: enough for the checks the bindings make on the host before they call it"""
+    from types import SimpleNamespace
+
+    from abcdez_amd.engine import HipOps
+
+    ops = object.__new__(HipOps)
+    ops.spec = SimpleNamespace(d=d)
+    return ops
+
+
+def blob_engine(oracle, n=16):
+    spec = A.ModelSpec(A.Normal(0.0, 2.0), A.Normal1D(1.5, 1.0, blobs=True), A.Epa0toeps, seed=3)
+    return oracle.oracle_engine(spec, n)
+
+
+def f64(*shape):
+    import torch
+
+    return torch.zeros(shape, dtype=torch.float64)
+
+
+def rerun_with_another_distance(oracle):
+    eng = blob_engine(oracle)
+    eng.init_population()
+    eng.reset_weights()
+    honest = eng.ops.blob_eval
+
+    def blob_eval(theta, stamp, blob, delta_out):
+        honest(theta, stamp, blob, delta_out)
+        delta_out[3] += 1.0
+    eng.ops.blob_eval = blob_eval
+    eng.result()
+
+
+def fake_engine_sample(oracle):
+    from types import SimpleNamespace
+
+    res = dict(P=np.arange(4.0), C=np.zeros(4), Wns=np.full(4, 0.25), blobs=None)
+    S.engine_sample(SimpleNamespace(result=lambda: res, spec=SimpleNamespace(seed=1)), 2, blobs=True)
+
+
+REFUSALS = {
+    "summary option": (lambda o: S.summary_options(dict(bins=1, median=True)), ValueError,
+                       "summary: unknown option(s) ['bins', 'median'] (cov, corrected, quantiles, wquantiles, hist)"),
+    "summary type": (lambda o: S.summary_options(3), ValueError,
+                     "summary must be None, True or a dict of the options cov, corrected, quantiles, wquantiles, hist"),
+    "predictive option": (lambda o: S.predictive_options(dict(quantiles=(0.5,))), ValueError,
+                          "predictive: unknown option(s) ['quantiles'] (cov, corrected, wquantiles, hist)"),
+    "predictive type": (lambda o: S.predictive_options(False), ValueError,
+                        "predictive must be None, True or a dict of the options cov, corrected, wquantiles, hist"),
+    "adjust option": (lambda o: S.adjust_options(dict(quantiles=(0.5,), bins=2)), ValueError,
+                      "adjust: unknown option(s) ['bins', 'quantiles'] (columns, target, ridge, cov, corrected, wquantiles, hist, rows)"),
+    "adjust type": (lambda o: S.adjust_options("all"), ValueError,
+                    "adjust must be None, True or a dict of the options columns, target, ridge, cov, corrected, wquantiles, hist, rows"),
+    "sample type": (lambda o: S.sample_options(True), ValueError,
+                    "sample must be None, an integer n or a dict of the options n, draw, blobs"),
+    "summary p": (lambda o: blob_engine(o).posterior_summary(quantiles=(0.5,), wquantiles=(1.5,)), ValueError, "summary: p must be in [0, 1]"),
+    "summary p, unweighted": (lambda o: blob_engine(o).posterior_summary(quantiles=(-0.5,)), ValueError, "summary: p must be in [0, 1]"),
+    "predictive p": (lambda o: blob_engine(o).posterior_predictive(wquantiles=(0.5, math.nan)), ValueError,
+                     "predictive: p must be in [0, 1]"),
+    "adjust p": (lambda o: blob_engine(o).posterior_adjusted(wquantiles=(2.0,)), ValueError, "adjust: p must be in [0, 1]"),
+    "posterior range": (lambda o: bare_ops().posterior_histograms(None, None, None, None, 5, range=[0.0, 1.0]), ValueError,
+                        "posterior_histograms: range must hold (lo, hi) per requested column"),
+    "columns range": (lambda o: bare_ops().columns_histograms(f64(5, 4), None, m=3, columns=[0, 2], range=[0.0, 1.0]), ValueError,
+                      "columns_histograms: range must hold (lo, hi) per requested column"),
+    "columns view": (lambda o: bare_ops()._columns_view(f64(5, 4).float(), None), ValueError,
+                     "columns: X must be a contiguous float64 matrix N x ldx"),
+    "columns view, through a call": (lambda o: bare_ops().columns_moments(f64(5, 4)[:, :2], None), ValueError,
+                                     "columns: X must be a contiguous float64 matrix N x ldx"),
+    "adjust blobs": (lambda o: bare_ops()._adjust_blobs(f64(5), None), ValueError, "adjust: Sb must be a contiguous float64 matrix N x lds"),
+    "adjust cross means": (lambda o: bare_ops().adjust_cross(None, None, None, None, 5, f64(5, 2), None, [0.0], [0.0] * 3), ValueError,
+                           "adjust: s_mean must hold one mean per chosen column and x_mean one per parameter"),
+    "adjust apply target": (lambda o: bare_ops().adjust_apply(None, None, None, None, 5, f64(5, 2), [1], [0.0], np.zeros((2, 3))), ValueError,
+                            "adjust: target must hold one number per chosen column and beta be c x d"),
+    "adjust apply Y": (lambda o: bare_ops().adjust_apply(None, None, None, None, 5, f64(5, 2), [1], [0.0], np.zeros((1, 3)), Y=f64(4, 3)),
+                       ValueError, "adjust: Y must be a contiguous float64 matrix N x ldy"),
+    "blob re-run": (rerun_with_another_distance, RuntimeError, "blobs: a re-run simulation does not reproduce the stored distance"),
+    "sample blobs": (fake_engine_sample, ValueError, "sample: blobs=True needs a simulator that returns blobs"),
+    "predictive matrix": (lambda o: S.predictive_reference(np.zeros((2, 2, 2))), ValueError,
+                          "predictive: blobs must be one row of numbers per particle"),
+    "adjust matrices": (lambda o: S.adjust_reference(np.zeros((3, 2)), np.zeros(4)), ValueError,
+                        "adjust: P and blobs must hold one row per particle"),
+    "summary weights": (lambda o: S.summary_reference(np.zeros(3), np.zeros(4)), ValueError, "summary: one weight per particle expected"),
+    "empty result": (lambda o: A.abcdesmc(PRIOR, SIM, 0.3, None, download=False, summary=False, engine=o.oracle_engine), ValueError,
+                     "download=False needs summary: the result would be empty"),
+}
+
+
+@pytest.mark.parametrize("name", list(REFUSALS))
+def test_refusal_strings_of_the_posterior_calls(oracle, name):
+    """the text of every refusal the host side of the posterior calls makes itself, as it stood before that code was shared"""
+    call, kind, text = REFUSALS[name]
+    with pytest.raises(kind) as e:
+        call(oracle)
+    assert type(e.value) is kind and str(e.value) == text
+
+
+def test_driver_keywords_are_checked_in_the_order_sample_predictive_adjust_summary(oracle):
+    bad = dict(sample=True, predictive=3, adjust="all", summary=3)
+    for first, prefix in (("sample", "sample must be"), ("predictive", "predictive must be"), ("adjust", "adjust must be"),
+                          ("summary", "summary must be")):
+        for run in (lambda **k: A.abcdesmc(PRIOR, SIM, 0.3, None, engine=oracle.oracle_engine, **k),
+                    lambda **k: A.abcdemc(PRIOR, SIM, 0.3, None, engine=oracle.oracle_engine, **k)):
+            with pytest.raises(ValueError) as e:
+                run(**bad)
+            assert str(e.value).startswith(prefix), (first, str(e.value))
+        del bad[first]
+
+
+def test_an_engine_object_without_the_posterior_calls_gets_the_restatements():
+    """the fallback of summary.engine_summary / _sample / _predictive / _adjusted: anything with result() and spec"""
+    from types import SimpleNamespace
+
+    rng = np.random.default_rng(4)
+    N = 300
+    P, B = rng.standard_normal((N, 2)), rng.standard_normal((N, 3))
+    w = rng.random(N) * (rng.random(N) > 0.2)
+    w /= w.sum()
+    res = dict(P=P, C=rng.random(N), Wns=w, blobs=B)
+    eng = SimpleNamespace(result=lambda: res, spec=SimpleNamespace(seed=7, sim=SimpleNamespace(data=lambda: (0.5, 0.0, -0.5))))
+    opts = dict(cov=True, wquantiles=(0.1, 0.9), hist=dict(bins=7))
+    for got, want in ((S.engine_summary(eng, **opts), S.summary_reference(P, w, **opts)),
+                      (S.engine_predictive(eng, **opts), S.predictive_reference(B, w, **opts)),
+                      (S.engine_adjusted(eng, **opts), S.adjust_reference(P, B, w, target=(0.5, 0.0, -0.5), **opts))):
+        for f in ("mean", "S", "cov", "wquantiles"):
+            assert getattr(got, f).tobytes() == getattr(want, f).tobytes(), f
+        assert (got.W, got.Q, got.n_pos, got.M, got.n_mass) == (want.W, want.Q, want.n_pos, want.M, want.n_mass)
+        assert np.array_equal(got.hist.mass1, want.hist.mass1)
+    s = S.engine_sample(eng, 11, draw=2)
+    index, M, n_mass = S.sample_reference(P, w, 11, 7, 2)
+    assert np.array_equal(s.index, index) and (s.M, s.n_mass, s.n, s.draw) == (M, n_mass, 11, 2)
+    assert np.array_equal(s.P, P[index]) and np.array_equal(s.C, res["C"][index]) and np.array_equal(s.blobs, B[index])
+    assert S.engine_sample(eng, 11, blobs=False).blobs is None
+    res["blobs"] = None
+    with pytest.raises(ValueError, match=r"predictive: needs a simulator that returns blobs \(blobs=True\)"):
+        S.engine_predictive(eng)
+    with pytest.raises(ValueError, match=r"adjust: needs a simulator that returns blobs \(blobs=True\)"):
+        S.engine_adjusted(eng)
