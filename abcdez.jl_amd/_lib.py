@@ -108,6 +108,11 @@ PROTOTYPES = {
                                   C.POINTER(C.c_uint64), _pi64],
     "abcdez_adjust_cross": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp],
     "abcdez_adjust_apply": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32],
+    "abcdez_adjust_transform": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32],
+    "abcdez_adjust_cross_dense": [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp],
+    "abcdez_adjust_logres": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32],
+    "abcdez_adjust_apply_scaled": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _i32],
     "abcdez_math_eval": [_vp, C.c_int, _vp, _vp, _vp, _i64],
     "abcdez_draws_eval": [_vp, C.c_int, _i64, _i64, _i64, _u32, _f64, _f64, _vp, _vp, _vp, _vp],
 }
@@ -117,12 +122,13 @@ HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _i64)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _vp, _vp, _i64, _i32, _i32)
 # symbols with a non-status return type
 OTHER_SYMBOLS = ("abcdez_version", "abcdez_rng_rounds", "abcdez_last_error", "abcdez_abi_layout")
-# added after MIN_VERSION (versions 620, 630, 640, 650, 660, 670): probed for, so that a 610 library still loads -- HipOps then lacks
-# the device summaries, a 640 library the device sample, a 650 library the column summaries (posterior predictive), a 660 library
-# the regression adjustment
+# added after MIN_VERSION (versions 620, 630, 640, 650, 660, 670, 680): probed for, so that a 610 library still loads -- HipOps then
+# lacks the device summaries, a 640 library the device sample, a 650 library the column summaries (posterior predictive), a 660
+# library the regression adjustment, a 670 library its transforms and heteroscedastic correction
 OPTIONAL_SYMBOLS = ("abcdez_posterior_moments", "abcdez_posterior_quantiles", "abcdez_posterior_wquantiles",
                     "abcdez_posterior_histograms", "abcdez_posterior_sample", "abcdez_columns_moments", "abcdez_columns_wquantiles",
-                    "abcdez_columns_histograms", "abcdez_adjust_cross", "abcdez_adjust_apply")
+                    "abcdez_columns_histograms", "abcdez_adjust_cross", "abcdez_adjust_apply", "abcdez_adjust_transform",
+                    "abcdez_adjust_cross_dense", "abcdez_adjust_logres", "abcdez_adjust_apply_scaled")
 
 
 class AbcdezError(RuntimeError):

@@ -108,10 +108,10 @@ extern "C" {
 
 /* 400: Philox4x32-10 again, abz_model.mv, group abort; 401: abcdemc's better particle by rejection;
  * 500: abcdez_comm_* and abcdez_smc_sweeps_sharded (RCCL behind the ABI), timing mode 3; 600: abcdez_comm_init_host (a host-supplied
- * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms; 650: abcdez_posterior_sample; 660: abcdez_columns_moments / _wquantiles / _histograms; 670: abcdez_adjust_cross / _apply.  Hosts refuse a library older than the
+ * transport under the same sharded entry points), librccl opened lazily; 610: abcdez_smc_generation_packed, abz_model.ext; 620: abcdez_posterior_moments / _quantiles; 630: abcdez_posterior_wquantiles; 640: abcdez_posterior_histograms; 650: abcdez_posterior_sample; 660: abcdez_columns_moments / _wquantiles / _histograms; 670: abcdez_adjust_cross / _apply; 680: abcdez_adjust_transform / _cross_dense / _logres / _apply_scaled.  Hosts refuse a library older than the
  * header they were written against (abcdez.jl_amd/_lib.py, julia/ABCdeZHIP.jl check_abi): a signature that grew an argument links
  * against an old binary without a diagnostic. */
-int abcdez_version(void) { return 670; }
+int abcdez_version(void) { return 680; }
 int abcdez_rng_rounds(void) { return ABZ_PHILOX_ROUNDS; }
 
 /* sizeof / offsetof of the two structs that cross the boundary, so that a host that mirrors them by hand (the Julia
@@ -1672,6 +1672,67 @@ int abcdez_adjust_apply(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const 
   if (adjust_args(ctx, bits, N, slot0, slot1, wns, Sb, lds, cols, n_cols, target && beta && Y, &p)) return -1;
   ABZ_REQUIRE(ldy >= p.d, "adjust: ldy must be at least length(prior)");
   return abz_adjust_apply_impl(ctx, p, Sb, lds, cols, n_cols, target, beta, Y, ldy);
+}
+
+/* Transforms and the heteroscedastic correction (csrc/abz_adjust_hcorr.hip).  The same arguments, the same checks and the same prefix. */
+static int adjust_transforms(int32_t d, const int32_t* tf_kind, const double* tf_lo_hi) {
+  ABZ_REQUIRE(tf_lo_hi, "adjust: transform: the kinds need the array of (lo, hi)");
+  for (int32_t k = 0; k < d; ++k) {
+    ABZ_REQUIRE(tf_kind[k] >= ABZ_ADJUST_TF_NONE && tf_kind[k] <= ABZ_ADJUST_TF_LOGIT,
+                "adjust: transform: unknown kind for parameter " + std::to_string(k) + " (0 identity, 1 log, 2 logit)");
+    if (tf_kind[k] == ABZ_ADJUST_TF_LOGIT) {
+      const double lo = tf_lo_hi[2 * k], hi = tf_lo_hi[2 * k + 1];
+      ABZ_REQUIRE(lo < hi && lo >= -DBL_MAX && hi <= DBL_MAX,
+                  "adjust: transform: logit of parameter " + std::to_string(k) + " needs finite bounds with lo < hi");
+    }
+  }
+  return 0;
+}
+
+int abcdez_adjust_transform(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                            const int32_t* tf_kind, const double* tf_lo_hi, double* U, int32_t ldu) {
+  SumPop p;
+  if (posterior_pop("adjust", ctx, bits, N, slot0, slot1, wns, tf_kind && tf_lo_hi && U, &p)) return -1;
+  if (adjust_transforms(p.d, tf_kind, tf_lo_hi)) return -1;
+  ABZ_REQUIRE(ldu >= p.d, "adjust: ldu must be at least length(prior)");
+  return abz_adjust_transform_impl(ctx, p, tf_kind, tf_lo_hi, U, ldu);
+}
+
+int abcdez_adjust_cross_dense(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N, const double* Sb,
+                              int32_t lds, const int32_t* cols, int32_t n_cols, const double* s_mean, const double* x_mean,
+                              double* S_out) {
+  ColView v;
+  if (columns_view("adjust", ctx, X, ldx, m, wns, N, Sb && s_mean && x_mean && S_out, &v)) return -1;
+  SumPop unused;
+  if (adjust_args(ctx, nullptr, N, X, nullptr, wns, Sb, lds, cols, n_cols, true, &unused)) return -1;
+  return abz_adjust_cross_dense_impl(ctx, v, Sb, lds, cols, n_cols, s_mean, x_mean, S_out);
+}
+
+int abcdez_adjust_logres(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1, const double* wns,
+                         const double* U, int32_t ldu, const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols,
+                         const double* s_mean, const double* x_mean, const double* beta, double* Z, int32_t ldz) {
+  SumPop p;
+  if (adjust_args(ctx, bits, N, slot0, slot1, wns, Sb, lds, cols, n_cols, s_mean && x_mean && beta && Z, &p)) return -1;
+  ABZ_REQUIRE(!U || ldu >= p.d, "adjust: ldu must be at least length(prior)");
+  ABZ_REQUIRE(ldz >= p.d, "adjust: ldz must be at least length(prior)");
+  ABZ_REQUIRE(Z != U, "adjust: Z must not be U");
+  return abz_adjust_logres_impl(ctx, p, U, ldu, Sb, lds, cols, n_cols, s_mean, x_mean, beta, Z, ldz);
+}
+
+int abcdez_adjust_apply_scaled(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                               const double* wns, const double* U, int32_t ldu, const double* Sb, int32_t lds, const int32_t* cols,
+                               int32_t n_cols, const double* target, const double* beta, const double* s_mean, const double* x_mean,
+                               const double* gamma, const double* m, const int32_t* tf_kind, const double* tf_lo_hi, double* Y,
+                               int32_t ldy) {
+  SumPop p;
+  if (adjust_args(ctx, bits, N, slot0, slot1, wns, Sb, lds, cols, n_cols, target && beta && Y, &p)) return -1;
+  ABZ_REQUIRE(!gamma || (s_mean && x_mean && m), "adjust: hcorr: gamma needs s_mean, x_mean and m");
+  if (tf_kind && adjust_transforms(p.d, tf_kind, tf_lo_hi)) return -1;
+  ABZ_REQUIRE(!U || ldu >= p.d, "adjust: ldu must be at least length(prior)");
+  ABZ_REQUIRE(ldy >= p.d, "adjust: ldy must be at least length(prior)");
+  ABZ_REQUIRE(Y != U, "adjust: Y must not be U");
+  return abz_adjust_apply_scaled_impl(ctx, p, U, ldu, Sb, lds, cols, n_cols, target, beta, s_mean, x_mean, gamma, m, tf_kind, tf_lo_hi, Y,
+                                      ldy);
 }
 
 int abcdez_math_eval(abcdez_ctx* ctx, int fn, const double* x, double* y, double* y2, int64_t n) {

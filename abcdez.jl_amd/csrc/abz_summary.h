@@ -1,4 +1,4 @@
-/* abz_summary.h -- what the posterior calls share (abz_summary.hip, abz_wquantile.hip, abz_hist.hip, abz_sample.hip, abz_adjust.hip
+/* abz_summary.h -- what the posterior calls share (abz_summary.hip, abz_wquantile.hip, abz_hist.hip, abz_sample.hip, abz_adjust.hip, abz_adjust_hcorr.hip
  * and their entry points in abz_api.hip): the view of a population, the two sources the gathers read their values from, the current
  * row and the integer mass of a position, a thread's share of a tile and the in-tile pairing of the sums, the tally of the masses
  * and its verdict, and the calls' buffer in the context. */
@@ -203,3 +203,13 @@ int abz_adjust_cross_impl(abcdez_ctx*, const SumPop&, const double* Sb, int lds,
                           const double* x_mean, double* S_sx_out);
 int abz_adjust_apply_impl(abcdez_ctx*, const SumPop&, const double* Sb, int lds, const int32_t* cols, int c, const double* target,
                           const double* beta, double* Y, int ldy);
+/* abz_adjust_hcorr.hip: tf_kind[d], tf_lo_hi[d][2], gamma[c d], m[d] are HOST arrays too, U, Z and Y DEVICE matrices; U == NULL: u is the
+ * population's push_p-cast parameters; gamma == NULL: no correction; tf_kind == NULL: no transform */
+int abz_adjust_transform_impl(abcdez_ctx*, const SumPop&, const int32_t* tf_kind, const double* tf_lo_hi, double* U, int ldu);
+int abz_adjust_cross_dense_impl(abcdez_ctx*, const ColView&, const double* Sb, int lds, const int32_t* cols, int c, const double* s_mean,
+                                const double* x_mean, double* S_out);
+int abz_adjust_logres_impl(abcdez_ctx*, const SumPop&, const double* U, int ldu, const double* Sb, int lds, const int32_t* cols, int c,
+                           const double* s_mean, const double* x_mean, const double* beta, double* Z, int ldz);
+int abz_adjust_apply_scaled_impl(abcdez_ctx*, const SumPop&, const double* U, int ldu, const double* Sb, int lds, const int32_t* cols, int c,
+                                 const double* target, const double* beta, const double* s_mean, const double* x_mean, const double* gamma,
+                                 const double* m, const int32_t* tf_kind, const double* tf_lo_hi, double* Y, int ldy);

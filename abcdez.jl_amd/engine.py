@@ -665,6 +665,99 @@ class HipOps:
             t.ctypes.data, b.ctypes.data, _ptr(Y), int(Y.shape[1])))
         return Y
 
+    # ---- transforms and the heteroscedastic correction of the regression adjustment (include/abcdez_hip.h, R4) ----
+    def _adjust_matrix(self, M, N, name, create=True):
+        """a DEVICE matrix N x ld (ld >= d) of the adjustment: checked, or created when None"""
+        if M is None and create:
+            M = torch.empty((int(N), self.spec.d), dtype=torch.float64, device=self.device)
+        if M is not None and (M.dim() != 2 or M.dtype != torch.float64 or not M.is_contiguous() or M.shape[0] != int(N)):
+            raise ValueError(f"adjust: {name} must be a contiguous float64 matrix N x ld")
+        return M
+
+    @staticmethod
+    def _adjust_tf(tf):
+        """(kind int32[d], lo_hi float64[d, 2]) of summary.adjust_transform, or None -> two host pointers (0: no transform) and
+        the arrays that must outlive the call"""
+        if tf is None:
+            return 0, 0, None
+        kind = np.ascontiguousarray(tf[0], dtype=np.int32).reshape(-1)
+        lo_hi = np.ascontiguousarray(tf[1], dtype=np.float64).reshape(-1)
+        return kind.ctypes.data, lo_hi.ctypes.data, (kind, lo_hi)
+
+    def adjust_transform(self, bits, slot0, slot1, wns, N, tf, U=None):
+        """U[N, d] (a DEVICE tensor; created when None): abz_adjust_forward of the push_p-cast parameters of the positions that
+        count, +0.0 for the others (abcdez_adjust_transform); ``tf``: (kind[d], lo_hi[d, 2]) of summary.adjust_transform"""
+        U = self._adjust_matrix(U, N, "U")
+        pk, pl, keep = self._adjust_tf(tf)
+        if keep is None or keep[0].size != self.spec.d or keep[1].size != 2 * self.spec.d:
+            raise ValueError("adjust: transform needs one kind and one (lo, hi) per parameter")
+        _lib.check(self.lib, self._summary_fn("abcdez_adjust_transform", 680)(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), pk, pl, _ptr(U), int(U.shape[1])))
+        return U
+
+    def adjust_cross_dense(self, X, wns, N, Sb, columns, s_mean, x_mean, m=None):
+        """S[c, m]: :meth:`adjust_cross` with the first m columns of the DEVICE matrix X[N][ldx] in the place of the parameters
+        (abcdez_adjust_cross_dense)"""
+        lds, cols = self._adjust_blobs(Sb, columns)
+        ldx, m = self._columns_view(X, m)
+        sm = np.ascontiguousarray(s_mean, dtype=np.float64).reshape(-1)
+        xm = np.ascontiguousarray(x_mean, dtype=np.float64).reshape(-1)
+        if sm.size != cols.size or xm.size != m:
+            raise ValueError("adjust: s_mean must hold one mean per chosen column and x_mean one per column of X")
+        out = np.empty((max(int(cols.size), 1), m), dtype=np.float64)
+        _lib.check(self.lib, self._summary_fn("abcdez_adjust_cross_dense", 680)(
+            self.ctx, _ptr(X), ldx, m, _ptr(wns), N, _ptr(Sb), lds, cols.ctypes.data, int(cols.size), sm.ctypes.data, xm.ctypes.data,
+            out.ctypes.data))
+        return out
+
+    def _adjust_vectors(self, cols, **named):
+        """host vectors of the adjustment, checked for their lengths: c per chosen column, d per parameter, c x d for coefficients"""
+        c, d = int(cols.size), self.spec.d
+        want = {"s_mean": (c,), "target": (c,), "x_mean": (d,), "m": (d,), "beta": (c, d), "gamma": (c, d)}
+        out = {}
+        for name, v in named.items():
+            if v is None:
+                out[name] = None
+                continue
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.size != int(np.prod(want[name])):
+                raise ValueError(f"adjust: {name} must have the shape {want[name]}")
+            out[name] = a
+        return out
+
+    def adjust_logres(self, bits, slot0, slot1, wns, N, U, Sb, columns, s_mean, x_mean, beta, Z=None):
+        """Z[N, d] (a DEVICE tensor; created when None): the log squared residuals of the first regression (abcdez_adjust_logres);
+        ``U``: the transformed parameters of :meth:`adjust_transform`, or None for the population's own"""
+        lds, cols = self._adjust_blobs(Sb, columns)
+        v = self._adjust_vectors(cols, s_mean=s_mean, x_mean=x_mean, beta=beta)
+        U = self._adjust_matrix(U, N, "U", create=False)
+        Z = self._adjust_matrix(Z, N, "Z")
+        _lib.check(self.lib, self._summary_fn("abcdez_adjust_logres", 680)(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), _ptr(U), int(U.shape[1]) if U is not None else 0, _ptr(Sb), lds,
+            cols.ctypes.data, int(cols.size), v["s_mean"].ctypes.data, v["x_mean"].ctypes.data, v["beta"].ctypes.data, _ptr(Z),
+            int(Z.shape[1])))
+        return Z
+
+    def adjust_apply_scaled(self, bits, slot0, slot1, wns, N, U, Sb, columns, target, beta, s_mean=None, x_mean=None, gamma=None, m=None,
+                            tf=None, Y=None):
+        """Y[N, d] (a DEVICE tensor; created when None; may be the Z of :meth:`adjust_logres`): the adjusted rows with the
+        heteroscedastic correction (``gamma``, ``m``, ``s_mean``, ``x_mean`` given) or without (all four None), transformed back
+        by ``tf`` (abcdez_adjust_apply_scaled)"""
+        lds, cols = self._adjust_blobs(Sb, columns)
+        if (gamma is None) != (m is None) or (gamma is None) != (s_mean is None) or (gamma is None) != (x_mean is None):
+            raise ValueError("adjust: gamma, m, s_mean and x_mean are given together or not at all")
+        v = self._adjust_vectors(cols, target=target, beta=beta, s_mean=s_mean, x_mean=x_mean, gamma=gamma, m=m)
+        hp = lambda a: 0 if a is None else a.ctypes.data
+        U = self._adjust_matrix(U, N, "U", create=False)
+        Y = self._adjust_matrix(Y, N, "Y")
+        pk, pl, keep = self._adjust_tf(tf)
+        _lib.check(self.lib, self._summary_fn("abcdez_adjust_apply_scaled", 680)(
+            self.ctx, _ptr(bits), N, _ptr(slot0), _ptr(slot1), _ptr(wns), _ptr(U), int(U.shape[1]) if U is not None else 0, _ptr(Sb), lds,
+            cols.ctypes.data, int(cols.size), hp(v["target"]), hp(v["beta"]), hp(v["s_mean"]), hp(v["x_mean"]), hp(v["gamma"]), hp(v["m"]),
+            pk, pl, _ptr(Y), int(Y.shape[1])))
+        del keep
+        return Y
+
     def set_stamps(self, cur, nxt):
         _lib.check(self.lib, self.lib.abcdez_ctx_set_stamps(self.ctx, _ptr(cur), _ptr(nxt)))
 
@@ -1608,7 +1701,7 @@ class PopulationEngine:
         return self._summarise(ColValues.of(X, self._weights(), nb), cov, corrected, (), wprobs, hist, hist_opts)
 
     def posterior_adjusted(self, columns=None, target=None, ridge: float = 0.0, cov: bool = True, corrected: bool = True, wquantiles=(),
-                           hist=None, rows: bool = False):
+                           hist=None, rows: bool = False, hcorr: bool = False, transform=None):
         """The regression-adjusted posterior (include/abcdez_spec.h, "REGRESSION ADJUSTMENT"): the local-linear ABC adjustment of
         Beaumont, Zhang and Balding (2002) -- `loclinear` of R's abc, `adjust_posterior` of pyABC and ELFI.  Every accepted particle
         is corrected for the gap between its simulation s_i (the blobs) and the observation, theta*_i = theta_i - beta^T (s_i -
@@ -1620,16 +1713,30 @@ class PopulationEngine:
         and ``beta`` (c x d), ``columns``, ``target``, ``ridge``, ``s_mean``, ``x_mean`` (the unadjusted mean), ``S_sx``; with
         ``rows=True`` also ``P`` (N x d adjusted rows, +0.0 for particles without weight).
 
-        The adjustment does not keep a discrete parameter integer, and adjusted values may leave the prior's support (the method's
-        known caveat; transforms are the user's business).  The regression weights are the population's: kernel weights for an
+        ``transform`` (R's ``transf``): None, one entry for every parameter or a list of d entries, each None, ``"log"`` or
+        ``("logit", lo, hi)`` with lo < hi finite.  The regression then runs on the transformed parameters and the adjusted rows are
+        transformed back before they are summarised: ``log`` rows are >= 0, ``logit`` rows lie in [lo, hi].  ``beta``, ``x_mean`` and
+        ``S_sx`` (and ``gamma``, ``z_mean``, ``S_sz``) of the record are then on the TRANSFORMED scale; the summaries and ``P`` are on
+        the parameters' own.  A particle that counts with a value outside a transform's domain (x <= 0 for log -- a zero count of a
+        discrete parameter included --, x <= lo or x >= hi for logit) is refused under a message that names ``transform`` and the
+        parameter.  ``hcorr=True`` (R's ``hcorr``, the heteroscedastic correction of Blum and Francois 2010): a second regression,
+        of the log squared residuals on the same simulated data, rescales every residual to the spread at the target,
+        theta*_i = m + e_i sigma(target) / sigma(s_i); the record carries its slopes ``gamma`` (c x d), ``z_mean`` and ``S_sz``
+        (None without it).  An exactly zero residual is refused by name.  With ``hcorr=False`` and ``transform=None`` the call does
+        exactly what it did before these options existed.
+
+        The adjustment does not keep a discrete parameter integer, and without a transform adjusted values may leave the prior's
+        support (the method's known caveat).  The regression weights are the population's: kernel weights for an
         Epanechnikov ABC kernel, uniform over the accepted particles for an indicator kernel.
 
         On the HIP engine the blobs are rebuilt on the device as :meth:`posterior_predictive` does, the moments of both halves, the
         cross moments (csrc/abz_adjust.hip) and the adjusted rows are computed there, the c x c solve runs on the host, and the
         adjusted rows are summarised by the column summaries and freed -- bit for bit
         :func:`abcdez_amd.summary.adjust_reference` of the downloaded result.  It needs N x (blob_width + d) x 8 bytes of device
-        memory for the two matrices while it runs, and changes nothing a continued run depends on.  Engines without the device
-        calls compute the restatement on ``result()``.  A simulator without blobs is refused."""
+        memory for the two matrices while it runs -- at most N x (blob_width + 2 d) x 8 with ``transform`` or ``hcorr`` (the
+        transformed parameters and the log residuals, over which the adjusted rows are written; csrc/abz_adjust_hcorr.hip) --
+        and changes nothing a continued run depends on.  Engines without the device calls compute the restatement on
+        ``result()``.  A simulator without blobs is refused."""
         from . import summary as _summary
 
         wprobs, = self._probabilities("adjust", wquantiles)
@@ -1639,28 +1746,55 @@ class PopulationEngine:
         cols = _summary.adjust_columns(columns, nb)
         t = _summary.adjust_target(target, cols, nb, tuple(self.spec.sim.data()))
         ridge = _summary.adjust_ridge(ridge)
+        hcorr = _summary.adjust_hcorr(hcorr)
+        tf = _summary.adjust_transform(transform, d)
         hist_opts = self._hist_options(hist, d)
-        if not hasattr(self.ops, "adjust_cross"):
+        extended = hcorr or tf is not None
+        if not hasattr(self.ops, "adjust_apply_scaled" if extended else "adjust_cross"):
             res = self.result()
             return _summary.adjust_reference(res["P"], res["blobs"], res["Wns"] if self.packed else None, target=t, columns=cols,
-                                             ridge=ridge, cov=cov, corrected=corrected, wquantiles=wprobs, hist=hist, rows=rows)
+                                             ridge=ridge, cov=cov, corrected=corrected, wquantiles=wprobs, hist=hist, rows=rows,
+                                             hcorr=hcorr, transform=transform)
         self._stream()
         th, _, dl = self.state
         Sb = self._rebuild_blobs(th, self.stamp[self.cur], dl)
         pop = self._live_population()
         wns = self._weights()
-        x_mean = self.ops.posterior_moments(*pop, self.N, want_second=False)[0]
+        U = None
+        if tf is not None:                               # u in the place of x from here on: a dense source
+            U = self.ops.adjust_transform(*pop, self.N, tf)
+            x_mean = self.ops.columns_moments(U, wns, m=d, want_second=False)[0]
+            _summary.adjust_check_transformed(x_mean, tf)
+        else:
+            x_mean = self.ops.posterior_moments(*pop, self.N, want_second=False)[0]
         s_all, S_all = self.ops.columns_moments(Sb, wns, m=nb, want_second=True)[:2]
         s_mean = s_all[cols]
         _summary.adjust_check_means(s_mean, x_mean)
-        S_sx = self.ops.adjust_cross(*pop, self.N, Sb, cols, s_mean, x_mean)
-        beta = _summary.adjust_solve(S_all[np.ix_(cols, cols)], S_sx, ridge, cols)
-        Y = self.ops.adjust_apply(*pop, self.N, Sb, cols, t, beta)
-        del Sb
+        if U is None:
+            S_sx = self.ops.adjust_cross(*pop, self.N, Sb, cols, s_mean, x_mean)
+        else:
+            S_sx = self.ops.adjust_cross_dense(U, wns, self.N, Sb, cols, s_mean, x_mean, m=d)
+        S_ss = S_all[np.ix_(cols, cols)]
+        beta = _summary.adjust_solve(S_ss, S_sx, ridge, cols)
+        gamma = z_mean = S_sz = None
+        if hcorr:
+            Z = self.ops.adjust_logres(*pop, self.N, U, Sb, cols, s_mean, x_mean, beta)
+            z_mean = self.ops.columns_moments(Z, wns, m=d, want_second=False)[0]
+            _summary.adjust_check_logres(z_mean)
+            S_sz = self.ops.adjust_cross_dense(Z, wns, self.N, Sb, cols, s_mean, z_mean, m=d)
+            gamma = _summary.adjust_solve(S_ss, S_sz, ridge, cols)
+            Y = self.ops.adjust_apply_scaled(*pop, self.N, U, Sb, cols, t, beta, s_mean=s_mean, x_mean=x_mean, gamma=gamma,
+                                             m=_summary.adjust_centre(x_mean, beta, s_mean, t), tf=tf, Y=Z)      # Y over Z, in place
+            del Z
+        elif tf is not None:
+            Y = self.ops.adjust_apply_scaled(*pop, self.N, U, Sb, cols, t, beta, tf=tf)
+        else:
+            Y = self.ops.adjust_apply(*pop, self.N, Sb, cols, t, beta)
+        del Sb, U
         rec = self._summarise(ColValues.of(Y, wns, d), cov, corrected, (), wprobs, hist, hist_opts)
         Ph = self._to_host([Y])[0] if rows else None
         del Y
-        return _summary.make_adjusted(rec, beta, cols, t, ridge, s_mean, x_mean, S_sx, Ph)
+        return _summary.make_adjusted(rec, beta, cols, t, ridge, s_mean, x_mean, S_sx, Ph, hcorr, tf, gamma, z_mean, S_sz)
 
     def _to_host(self, tensors):
         """device tensors -> numpy arrays.  On the GPU: contiguous copies into PINNED host memory, all enqueued back to back on

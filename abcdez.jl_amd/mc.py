@@ -30,7 +30,7 @@ def abcdemc(prior, dist, ϵ_target, varexternal=None, *,
     ``summary`` / ``download``: as in :func:`abcdesmc` (abcdemc has no weights: every particle counts once).
     ``sample=n | dict(n=, draw=, blobs=)``: as in :func:`abcdesmc`, ``r.sample`` (unit masses: the closed form of the spec).
     ``predictive=True | dict(cov=, corrected=, wquantiles=, hist=)``: as in :func:`abcdesmc`, ``r.predictive`` (unit weights).
-    ``adjust=True | dict(columns=, target=, ridge=, cov=, corrected=, wquantiles=, hist=, rows=)``: as in :func:`abcdesmc`,
+    ``adjust=True | dict(columns=, target=, ridge=, cov=, corrected=, wquantiles=, hist=, rows=, hcorr=, transform=)``: as in :func:`abcdesmc`,
     ``r.adjusted`` (unit weights: an ordinary least-squares adjustment over all particles).
     """
     post_opts = _posterior_options(summary, download, sample, predictive, adjust)

@@ -184,7 +184,9 @@ def abcdesmc(prior, dist, ϵ_target, varexternal=None, *,
     where the population lives; it needs a simulator with blobs and, like ``summary`` and ``sample``, goes with ``download=False``.
 
     Regression adjustment: ``adjust=True`` (or a dict of the options ``columns``, ``target``, ``ridge``, ``cov``, ``corrected``,
-    ``wquantiles``, ``hist``, ``rows`` of :meth:`PopulationEngine.posterior_adjusted`) puts the local-linear regression-adjusted
+    ``wquantiles``, ``hist``, ``rows``, ``hcorr``, ``transform`` of :meth:`PopulationEngine.posterior_adjusted`; ``hcorr=True`` adds
+    the heteroscedastic correction of Blum and Francois (2010), ``transform="log"`` or ``("logit", lo, hi)`` keeps the adjusted
+    values inside the parameters' support) puts the local-linear regression-adjusted
     posterior (Beaumont, Zhang and Balding 2002) into ``r.adjusted``: every accepted particle corrected for the gap between its
     simulation and the observation, theta - beta^T (s - target), and summarised where the population lives.  A run may then stop
     at a larger ϵ_target for the same accuracy.  It needs a simulator with blobs and goes with ``download=False``.

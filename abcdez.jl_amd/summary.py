@@ -11,7 +11,9 @@ from __future__ import annotations
 
 import bisect
 import math
+import struct
 from builtins import range as builtins_range     # hist_reference has a `range` argument
+from fractions import Fraction
 from types import SimpleNamespace
 
 import numpy as np
@@ -74,16 +76,18 @@ def _as_matrix(v):
     return X[:, None] if X.ndim == 1 else X
 
 
-def _options(who: str, value, allowed) -> dict:
-    """a driver keyword that is True (the defaults) or a dict of the options ``allowed`` -> a copy of the dict"""
+def _options(who: str, value, allowed, named=None) -> dict:
+    """a driver keyword that is True (the defaults) or a dict of the options ``allowed`` -> a copy of the dict.  ``named``: the
+    options the two refusals list, where their wording is older than the newest options (default: all of them)"""
+    named = allowed if named is None else named
     if value is True:
         return {}
     if isinstance(value, dict):
         bad = set(value) - set(allowed)
         if bad:
-            raise ValueError(f"{who}: unknown option(s) {sorted(bad)} ({', '.join(allowed)})")
+            raise ValueError(f"{who}: unknown option(s) {sorted(bad)} ({', '.join(named)})")
         return dict(value)
-    raise ValueError(f"{who} must be None, True or a dict of the options {', '.join(allowed)}")
+    raise ValueError(f"{who} must be None, True or a dict of the options {', '.join(named)}")
 
 
 def engine_call(eng, method: str, fallback, **opts):
@@ -543,7 +547,7 @@ def engine_predictive(eng, **opts):
 
 
 # ------------------------------------------------------------------ regression adjustment (include/abcdez_spec.h, "REGRESSION ADJUSTMENT")
-ADJUST_OPTIONS = ("columns", "target", "ridge", "cov", "corrected", "wquantiles", "hist", "rows")
+ADJUST_OPTIONS = ("columns", "target", "ridge", "cov", "corrected", "wquantiles", "hist", "rows", "hcorr", "transform")
 ADJUST_NEEDS_BLOBS = "adjust: needs a simulator that returns blobs (blobs=True)"
 ADJUST_MAX_C = 256              # ABZ_ADJUST_MAX_C
 ADJUST_PIVOT = 2.0 ** -40       # a pivot must exceed this fraction of its diagonal entry
@@ -551,8 +555,8 @@ ADJUST_PIVOT = 2.0 ** -40       # a pivot must exceed this fraction of its diago
 
 def adjust_options(adjust) -> dict:
     """the ``adjust=`` keyword of the drivers: True, or a dict of columns / target / ridge / cov / corrected / wquantiles / hist /
-    rows -> the keywords of posterior_adjusted"""
-    return _options("adjust", adjust, ADJUST_OPTIONS)
+    rows / hcorr / transform -> the keywords of posterior_adjusted"""
+    return _options("adjust", adjust, ADJUST_OPTIONS, ADJUST_OPTIONS[:8])      # the refusals keep their wording of version 670
 
 
 def adjust_columns(columns, n_blob: int):
@@ -661,10 +665,239 @@ def adjust_apply(X, B, live, target, beta):
         return np.where(live[:, None], Xl - acc, 0.0)
 
 
-def make_adjusted(rec, beta, columns, target, ridge, s_mean, x_mean, S_sx, P=None):
+# ---- transforms and the heteroscedastic correction (include/abcdez_spec.h, "REGRESSION ADJUSTMENT": TRANSFORM, HETEROSCEDASTIC CORRECTION)
+TF_NONE, TF_LOG, TF_LOGIT = 0, 1, 2             # ABZ_ADJUST_TF_*
+_TF_NAMES = {TF_NONE: "identity", TF_LOG: "log", TF_LOGIT: "logit"}
+
+
+def adjust_hcorr(hcorr) -> bool:
+    """the ``hcorr`` option: False or True"""
+    if not isinstance(hcorr, (bool, np.bool_)):
+        raise ValueError("adjust: hcorr must be False or True")
+    return bool(hcorr)
+
+
+def _transform_entry(entry):
+    if entry is None:
+        return TF_NONE, 0.0, 0.0
+    if isinstance(entry, str):
+        if entry == "log":
+            return TF_LOG, 0.0, 0.0
+        if entry == "logit":
+            raise ValueError('adjust: transform: a logit needs its bounds, ("logit", lo, hi)')
+        raise ValueError(f'adjust: transform: unknown transform {entry!r} (None, "log" or ("logit", lo, hi))')
+    if isinstance(entry, (tuple, list)) and len(entry) == 3 and entry[0] == "logit":
+        try:
+            lo, hi = float(entry[1]), float(entry[2])
+        except (TypeError, ValueError):
+            raise ValueError('adjust: transform: the bounds of ("logit", lo, hi) must be numbers') from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+            raise ValueError('adjust: transform: ("logit", lo, hi) needs finite bounds with lo < hi')
+        return TF_LOGIT, lo, hi
+    raise ValueError(f'adjust: transform: unknown transform {entry!r} (None, "log" or ("logit", lo, hi))')
+
+
+def adjust_transform(transform, d: int):
+    """the ``transform`` option -> None (every transform is the identity) or (kind int32[d], lo_hi float64[d, 2]).  ``transform`` is
+    None, one entry for every parameter, or a list of d entries; an entry is None, "log" or ("logit", lo, hi) with lo < hi finite"""
+    if transform is None:
+        return None
+    single = isinstance(transform, str) or (isinstance(transform, tuple) and len(transform) == 3 and transform[0] == "logit")
+    entries = [transform] * d if single else transform
+    if not isinstance(entries, (list, tuple)):
+        raise ValueError(f'adjust: transform: unknown transform {transform!r} (None, "log" or ("logit", lo, hi))')
+    if len(entries) != d:
+        raise ValueError(f"adjust: transform must be one entry or a list of {d} entries, one per parameter")
+    got = [_transform_entry(e) for e in entries]
+    kind = np.array([g[0] for g in got], dtype=np.int32)
+    if not kind.any():
+        return None
+    return kind, np.array([[g[1], g[2]] for g in got], dtype=np.float64).reshape(d, 2)
+
+
+def _fma(a: float, b: float, c: float) -> float:
+    """abz_fma of finite doubles: a b + c rounded once (exact rationals; the conversion of a Fraction to float rounds to nearest even)"""
+    r = Fraction(a) * Fraction(b) + Fraction(c)
+    if r == 0:
+        return a * b + c                                # exact, and it carries the sign IEEE gives the zero
+    return float(r)
+
+
+def _d2u(x: float) -> int:
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def _u2d(u: int) -> float:
+    return struct.unpack("<d", struct.pack("<Q", u & 0xFFFFFFFFFFFFFFFF))[0]
+
+
+_NAN = _u2d(0x7FF8000000000000)                          # ABZ_NAN
+
+
+def abz_log(x: float) -> float:
+    """abz_log of include/abcdez_spec.h, literally (abz_log_core inlined)"""
+    ux = _d2u(x)
+    k = 0
+    if (ux << 1) & 0xFFFFFFFFFFFFFFFF == 0:
+        return -math.inf
+    if ux >> 63:
+        return _NAN
+    if (ux >> 52) == 0x7FF:
+        return x
+    if (ux >> 52) == 0:
+        x = x * 2.0 ** 54
+        ux = _d2u(x)
+        k = -54
+    hx = ux >> 32
+    hx = (hx + (0x3FF00000 - 0x3FE6A09E)) & 0xFFFFFFFF
+    k += (hx >> 20) - 0x3FF
+    hx = (hx & 0x000FFFFF) + 0x3FE6A09E
+    m = _u2d((hx << 32) | (ux & 0xFFFFFFFF))
+    f = m - 1.0
+    s = f / (2.0 + f)
+    z = s * s
+    R = 1.479819860511658591e-01
+    for c in (1.531383769920937332e-01, 1.818357216161805012e-01, 2.222219843214978396e-01, 2.857142874366239149e-01,
+              3.999999999940941908e-01, 6.666666666666735130e-01):
+        R = _fma(R, z, c)
+    R = R * z
+    hfsq = 0.5 * f * f
+    dk = float(k)
+    ln2_hi, ln2_lo = 6.93147180369123816490e-01, 1.90821492927058770002e-10
+    return dk * ln2_hi - ((hfsq - _fma(s, hfsq + R, dk * ln2_lo)) - f)
+
+
+def abz_exp(x: float) -> float:
+    """abz_exp of include/abcdez_spec.h, literally"""
+    if x != x:
+        return x
+    if x > 709.782712893383973096:
+        return math.inf
+    if x < -745.13321910194110842:
+        return 0.0
+    invln2 = 1.44269504088896338700e+00
+    ln2_hi, ln2_lo = 6.93147180369123816490e-01, 1.90821492927058770002e-10
+    t = x * invln2
+    k = int(t + (-0.5 if x < 0.0 else 0.5))             # the C cast truncates toward zero, as int() does
+    dk = float(k)
+    hi = _fma(-dk, ln2_hi, x)
+    lo = dk * ln2_lo
+    r = hi - lo
+    rr = r * r
+    P = 4.13813679705723846039e-08
+    for c in (-1.65339022054652515390e-06, 6.61375632143793436117e-05, -2.77777777770155933842e-03, 1.66666666666666019037e-01):
+        P = _fma(P, rr, c)
+    c = _fma(-P, rr, r)
+    y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi)
+    if k > 1000:
+        y = y * 2.0 ** 1000
+        k -= 1000
+    elif k < -1000:
+        y = y * 2.0 ** -1000
+        k += 1000
+    return y * _u2d((k + 1023) << 52)
+
+
+def _elementwise(f):
+    def g(a):
+        a = np.asarray(a, dtype=np.float64)
+        flat = a.reshape(-1)
+        return np.array([f(float(v)) for v in flat], dtype=np.float64).reshape(a.shape)
+    return g
+
+
+ADJUST_MATH = (_elementwise(abz_log), _elementwise(abz_exp))      # the default ``math`` pair: the spec's own log and exp
+
+
+def adjust_forward(X, tf, math=ADJUST_MATH):
+    """abz_adjust_forward of every value: U (n x d) from the push_p-cast rows X of the positions that count"""
+    if tf is None:
+        return X
+    kind, lo_hi = tf
+    log = math[0]
+    U = np.array(X, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for k in range(U.shape[1]):
+            if kind[k] == TF_LOG:
+                U[:, k] = log(X[:, k])
+            elif kind[k] == TF_LOGIT:
+                U[:, k] = log((X[:, k] - lo_hi[k, 0]) / (lo_hi[k, 1] - X[:, k]))
+    return U
+
+
+def adjust_back(V, tf, math=ADJUST_MATH):
+    """abz_adjust_back of every value"""
+    if tf is None:
+        return V
+    kind, lo_hi = tf
+    exp = math[1]
+    Y = np.array(V, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for k in range(Y.shape[1]):
+            if kind[k] == TF_LOG:
+                Y[:, k] = exp(V[:, k])
+            elif kind[k] == TF_LOGIT:
+                Y[:, k] = lo_hi[k, 0] + (lo_hi[k, 1] - lo_hi[k, 0]) / (1.0 + exp(-V[:, k]))
+    return Y
+
+
+def adjust_check_transformed(u_mean, tf):
+    """a counting row outside the domain of its transform makes the mean of its column non-finite: refused before the cross pass"""
+    if tf is None:
+        return
+    for k in np.flatnonzero(~np.isfinite(u_mean)):
+        if tf[0][k] != TF_NONE:
+            raise ValueError(f"adjust: transform: parameter {int(k)} has a value outside the domain of its {_TF_NAMES[int(tf[0][k])]} "
+                             "transform among the particles that count (log needs x > 0, logit lo < x < hi)")
+
+
+def adjust_check_logres(z_mean):
+    for k in np.flatnonzero(~np.isfinite(z_mean)):
+        raise ValueError(f"adjust: hcorr: a residual of parameter {int(k)} is exactly zero or not finite (its log is not finite)")
+
+
+def adjust_centre(x_mean, beta, s_mean, target):
+    """m_k = xmean_k - sum_j beta_jk (smean_j - t_j), j ascending from +0.0: the fitted value at the target"""
+    acc = np.zeros(beta.shape[1])
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(beta.shape[0]):
+            acc = acc + beta[j] * (s_mean[j] - target[j])
+        return np.asarray(x_mean, dtype=np.float64) - acc
+
+
+def adjust_residual(U, B, live, s_mean, x_mean, beta):
+    """E (N x d): e_i = (u_i - xmean) - sum_j beta[j] (B[i, j] - smean[j]), j ascending from +0.0, for the rows with ``live``; +0.0
+    for the others, whose inputs are never read"""
+    Ul = np.where(live[:, None], U, 0.0)
+    Bl = np.where(live[:, None], B, 0.0)
+    acc = np.zeros_like(Ul)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(B.shape[1]):
+            acc = acc + beta[j][None, :] * (Bl[:, j] - s_mean[j])[:, None]
+        return np.where(live[:, None], (Ul - x_mean) - acc, 0.0)
+
+
+def adjust_scaled(E, B, live, target, gamma, m, math=ADJUST_MATH):
+    """V (N x d): v_i = m + e_i exp(-0.5 sum_j gamma[j] (B[i, j] - target[j])) for the rows with ``live``, +0.0 for the others"""
+    Bl = np.where(live[:, None], B, 0.0)
+    acc = np.zeros_like(E)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(B.shape[1]):
+            acc = acc + gamma[j][None, :] * (Bl[:, j] - target[j])[:, None]
+        V = np.zeros_like(E)
+        V[live] = m + E[live] * math[1](-0.5 * acc[live])
+    return V
+
+
+def make_adjusted(rec, beta, columns, target, ridge, s_mean, x_mean, S_sx, P=None, hcorr=False, transform=None, gamma=None, z_mean=None,
+                  S_sz=None):
     """the record ``posterior_adjusted`` returns: the fields of :func:`make_summary` for the adjusted parameters (``rec``) and
     ``beta`` (c x d), ``columns``, ``target``, ``ridge``, ``s_mean`` (c), ``x_mean`` (d: the unadjusted weighted mean), ``S_sx``
-    (c x d), ``P`` (N x d adjusted rows, +0.0 for particles without weight; None unless asked for)"""
+    (c x d), ``P`` (N x d adjusted rows, +0.0 for particles without weight; None unless asked for); ``hcorr`` and, when it is on,
+    ``gamma`` (c x d: the slopes of the log squared residuals), ``z_mean`` (d) and ``S_sz`` (c x d), None otherwise; ``transform``:
+    None, or the tuple of the d entries (None, "log" or ("logit", lo, hi)).  With a transform ``beta``, ``x_mean``, ``S_sx`` (and
+    ``gamma``, ``z_mean``, ``S_sz``) are on the TRANSFORMED scale; ``mean``, ``cov``, the quantiles, ``hist`` and ``P`` are on the
+    parameters' own."""
     c = len(columns)
     out = SimpleNamespace(**vars(rec))
     out.beta = np.asarray(beta, dtype=np.float64).reshape(c, -1)
@@ -675,17 +908,26 @@ def make_adjusted(rec, beta, columns, target, ridge, s_mean, x_mean, S_sx, P=Non
     out.x_mean = np.asarray(x_mean, dtype=np.float64).reshape(-1)
     out.S_sx = np.asarray(S_sx, dtype=np.float64).reshape(c, -1)
     out.P = P
+    out.hcorr = bool(hcorr)
+    out.transform = None if transform is None else tuple(
+        None if kd == TF_NONE else "log" if kd == TF_LOG else ("logit", float(lh[0]), float(lh[1])) for kd, lh in zip(*transform))
+    out.gamma = None if gamma is None else np.asarray(gamma, dtype=np.float64).reshape(c, -1)
+    out.z_mean = None if z_mean is None else np.asarray(z_mean, dtype=np.float64).reshape(-1)
+    out.S_sz = None if S_sz is None else np.asarray(S_sz, dtype=np.float64).reshape(c, -1)
     return out
 
 
 def adjust_reference(P, blobs, Wns=None, target=None, columns=None, ridge=0.0, cov=True, corrected=True, wquantiles=(), hist=None,
-                     rows=False, data=None):
+                     rows=False, data=None, hcorr=False, transform=None, math=None):
     """numpy restatement of the regression-adjusted posterior (include/abcdez_spec.h, "REGRESSION ADJUSTMENT"), literally: ``P``
     the push_p-cast population (``r.P``), ``blobs`` the simulated data behind it (``r.blobs``), ``Wns`` the weights (None: unit
     weights, abcdemc), ``target`` one number per chosen column (None: ``data``, the simulator's ``data()``, when it has one number
     per blob column).  Moments by :func:`summary_reference`, the cross moments by :func:`tile_tree_sum`, the solve by
     :func:`adjust_solve`, and the summaries of the adjusted rows by :func:`summary_reference` again.  Rows of particles without
-    weight may hold anything.  Returns the record of :func:`make_adjusted`."""
+    weight may hold anything.  ``hcorr`` and ``transform`` (the options of :func:`adjust_hcorr` / :func:`adjust_transform`) restate
+    the spec's HETEROSCEDASTIC CORRECTION and TRANSFORM; ``math`` is the pair (log, exp) over float64 arrays they use, by default the
+    literal :func:`abz_log` / :func:`abz_exp` (bit for bit the device's; slow -- a test passes the oracle's, a law test numpy's).
+    With both options off nothing changes.  Returns the record of :func:`make_adjusted`."""
     if blobs is None:
         raise ValueError(ADJUST_NEEDS_BLOBS)
     X, B = _as_matrix(P), _as_matrix(blobs)
@@ -696,24 +938,56 @@ def adjust_reference(P, blobs, Wns=None, target=None, columns=None, ridge=0.0, c
     cols = adjust_columns(columns, nb)
     t = adjust_target(target, cols, nb, data)
     ridge = adjust_ridge(ridge)
-    mx = summary_reference(X, Wns, cov=False)
-    ms = summary_reference(B, Wns, cov=True)
+    hcorr = adjust_hcorr(hcorr)
+    tf = adjust_transform(transform, d)
+    math = ADJUST_MATH if math is None else math
     w = np.ones(N) if Wns is None else np.asarray(Wns, dtype=np.float64)
+    if w.shape != (N,):
+        raise ValueError("summary: one weight per particle expected")
     live = w > 0.0
     wl = np.where(live, w, 0.0)
+    if tf is not None:                                  # U: rows that do not count are +0.0 and never read
+        U = np.zeros((N, d))
+        U[live] = adjust_forward(X[live], tf, math)
+        X = U
+    mx = summary_reference(X, Wns, cov=False)
+    ms = summary_reference(B, Wns, cov=True)
     Bc = B[:, cols]
     s_mean, x_mean = ms.mean[cols], mx.mean
+    adjust_check_transformed(x_mean, tf)
     adjust_check_means(s_mean, x_mean)
-    with np.errstate(over="ignore", invalid="ignore"):
-        Cs = np.where(live[:, None], Bc, 0.0) - s_mean
-        Cx = np.where(live[:, None], X, 0.0) - x_mean
-        S_sx = np.empty((len(cols), d))
-        for j in range(len(cols)):
-            S_sx[j] = tile_tree_sum(np.where(live[:, None], wl[:, None] * (Cs[:, j:j + 1] * Cx), 0.0))
-    beta = adjust_solve(ms.S[np.ix_(cols, cols)], S_sx, ridge, cols)
-    Y = adjust_apply(X, Bc, live, t, beta)
+
+    def cross(V, v_mean):
+        with np.errstate(over="ignore", invalid="ignore"):
+            Cs = np.where(live[:, None], Bc, 0.0) - s_mean
+            Cv = np.where(live[:, None], V, 0.0) - v_mean
+            out = np.empty((len(cols), d))
+            for j in range(len(cols)):
+                out[j] = tile_tree_sum(np.where(live[:, None], wl[:, None] * (Cs[:, j:j + 1] * Cv), 0.0))
+        return out
+
+    S_sx = cross(X, x_mean)
+    S_ss = ms.S[np.ix_(cols, cols)]
+    beta = adjust_solve(S_ss, S_sx, ridge, cols)
+    gamma = z_mean = S_sz = None
+    if hcorr:
+        E = adjust_residual(X, Bc, live, s_mean, x_mean, beta)
+        Z = np.zeros((N, d))
+        with np.errstate(all="ignore"):
+            Z[live] = math[0](E[live] * E[live])
+        z_mean = summary_reference(Z, Wns, cov=False).mean
+        adjust_check_logres(z_mean)
+        S_sz = cross(Z, z_mean)
+        gamma = adjust_solve(S_ss, S_sz, ridge, cols)
+        V = adjust_scaled(E, Bc, live, t, gamma, adjust_centre(x_mean, beta, s_mean, t), math)
+    else:
+        V = adjust_apply(X, Bc, live, t, beta)
+    Y = V
+    if tf is not None:
+        Y = np.zeros((N, d))
+        Y[live] = adjust_back(V[live], tf, math)
     rec = summary_reference(Y, Wns, cov=cov, corrected=corrected, quantiles=(), wquantiles=wquantiles, hist=hist)
-    return make_adjusted(rec, beta, cols, t, ridge, s_mean, x_mean, S_sx, Y if rows else None)
+    return make_adjusted(rec, beta, cols, t, ridge, s_mean, x_mean, S_sx, Y if rows else None, hcorr, tf, gamma, z_mean, S_sz)
 
 
 def engine_adjusted(eng, **opts):

@@ -5,6 +5,9 @@ carries the simulated data behind its distance; ``adjust=dict(wquantiles=(0.025,
 data under the population's weights and moves every particle to where it would sit had its simulation hit the observation,
 θ - βᵀ(s - s_obs) -- on the device, next to the raw summary of the same population.  The raw band of a loose ϵ is wide; the adjusted
 band is what a much tighter (and much more expensive) ϵ would give.  ``ridge`` keeps the 20 x 20 normal equations well posed.
+The rate constants are positive, and a straight line subtracted from them need not be: the second table repeats the adjustment on
+the same engine with ``transform="log"`` (the regression runs on log θ and the rows are transformed back, so none is negative) and
+``hcorr=True`` (the heteroscedastic correction of Blum and François 2010: residuals rescaled to the spread at the observation).
 
     python examples/regression_adjustment.py [nparticles] [ϵ]
 """
@@ -37,6 +40,13 @@ def main():
     for k, name in enumerate("abce"):
         a, b = raw.wquantiles[:, k], adj.wquantiles[:, k]
         print(f" {name}  {TRUE[k]:7.3f}    {a[0]:9.3f} {a[1]:9.3f} {a[2]:9.3f}   |       {b[0]:9.3f} {b[1]:9.3f} {b[2]:9.3f}   {(b[2] - b[0]) / (a[2] - a[0]):9.2f}")
+    low = (0.0,) + PROBS
+    plain = r.engine.posterior_adjusted(cov=False, wquantiles=low, ridge=1e-6)
+    logged = r.engine.posterior_adjusted(cov=False, wquantiles=low, ridge=1e-6, transform="log", hcorr=True)
+    print(' θ    plain: smallest adjusted value   |  transform="log", hcorr=True: smallest     2.5 %    median    97.5 %')
+    for k, name in enumerate("abce"):
+        b = logged.wquantiles[:, k]
+        print(f" {name}            {plain.wquantiles[0, k]:9.3f}              |                          {b[0]:9.3f} {b[1]:9.3f} {b[2]:9.3f} {b[3]:9.3f}")
 
 
 if __name__ == "__main__":

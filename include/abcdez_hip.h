@@ -545,6 +545,41 @@ ABCDEZ_API int abcdez_adjust_apply(abcdez_ctx* ctx, const uint32_t* bits, int64_
                                    const double* wns, const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols,
                                    const double* target, const double* beta, double* Y, int32_t ldy);
 
+/* R4  Bounded transforms and the heteroscedastic correction of R3 (library version 680): `transf = "log" | "logit"` and `hcorr = TRUE`
+ *     of R's abc (Blum and Francois 2010).  Arithmetic: abcdez_spec.h, "posterior summaries" (REGRESSION ADJUSTMENT: TRANSFORM,
+ *     HETEROSCEDASTIC CORRECTION).  The population, Sb, cols and the weights are those of R3; U, Z and Y are DEVICE matrices N x ld*
+ *     with ld* >= length(prior) = d, rows of positions that do not count +0.0 and never read.  Transforms: tf_kind[d] (HOST; 0
+ *     identity, 1 log, 2 logit) and tf_lo_hi[d][2] (HOST; the bounds of a logit, lo < hi finite; ignored otherwise).  Every call
+ *     only reads the population, Sb and U, stages its host vectors in the summaries' buffer and synchronises once; the whole
+ *     adjustment needs at most N x (lds + 2 d) x 8 bytes (Sb, U and Z; Y may be written over Z).  Refusals: prefix "adjust:".
+ *     adjust_transform (spec: TRANSFORM, abz_adjust_forward): U[i][k] = forward_k(push_p of parameter k of position i).  A value
+ *       outside the domain of its transform becomes -Inf, +Inf or NaN; the host finds it in the mean of U.                   */
+ABCDEZ_API int abcdez_adjust_transform(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                       const double* wns, const int32_t* tf_kind, const double* tf_lo_hi, double* U, int32_t ldu);
+/*     adjust_cross_dense (spec: REGRESSION ADJUSTMENT, S_sx; HETEROSCEDASTIC CORRECTION, S_sz): abcdez_adjust_cross with the first m
+ *       columns of the dense matrix X[N][ldx] (U or Z; the arguments of abcdez_columns_moments) in the place of the parameters:
+ *       S_out[n_cols][m] (HOST) = T(w (s_j - s_mean[j]) (X_k - x_mean[k])) -- the same kernel text over the other value source.   */
+ABCDEZ_API int abcdez_adjust_cross_dense(abcdez_ctx* ctx, const double* X, int32_t ldx, int32_t m, const double* wns, int64_t N,
+                                         const double* Sb, int32_t lds, const int32_t* cols, int32_t n_cols, const double* s_mean,
+                                         const double* x_mean, double* S_out);
+/*     adjust_logres (spec: HETEROSCEDASTIC CORRECTION, abz_adjust_residual / abz_adjust_logres): Z[i][k] = abz_log(e e) with
+ *       e = (u_ik - x_mean[k]) - sum_j beta[j][k] (s_i,cols[j] - s_mean[j]), j ascending; u is row i of U, or the push_p-cast
+ *       parameters when U is NULL.  s_mean[n_cols], x_mean[d], beta[n_cols][d] are HOST arrays and must be finite.           */
+ABCDEZ_API int abcdez_adjust_logres(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                    const double* wns, const double* U, int32_t ldu, const double* Sb, int32_t lds,
+                                    const int32_t* cols, int32_t n_cols, const double* s_mean, const double* x_mean,
+                                    const double* beta, double* Z, int32_t ldz);
+/*     adjust_apply_scaled (spec: HETEROSCEDASTIC CORRECTION, abz_adjust_scaled; TRANSFORM, abz_adjust_back): Y[i][k] = back_k(v_ik),
+ *       v_ik = m[k] + e exp(-0.5 sum_j gamma[j][k] (s_i,cols[j] - target[j])) with e as in adjust_logres; gamma == NULL (s_mean,
+ *       x_mean, m are then not read): v_ik = u_ik - sum_j beta[j][k] (s_i,cols[j] - target[j]), the arithmetic of adjust_apply.
+ *       tf_kind == NULL: no back-transform.  U as in adjust_logres; Y must not be U (it may be the Z of adjust_logres).  All vectors
+ *       are HOST arrays and must be finite.                                                                                  */
+ABCDEZ_API int abcdez_adjust_apply_scaled(abcdez_ctx* ctx, const uint32_t* bits, int64_t N, const double* slot0, const double* slot1,
+                                          const double* wns, const double* U, int32_t ldu, const double* Sb, int32_t lds,
+                                          const int32_t* cols, int32_t n_cols, const double* target, const double* beta,
+                                          const double* s_mean, const double* x_mean, const double* gamma, const double* m,
+                                          const int32_t* tf_kind, const double* tf_lo_hi, double* Y, int32_t ldy);
+
 /* Test hooks: evaluate the spec arithmetic on the device (fn: 0 log, 1 exp, 2 sincos2pi,
  * 3 rint, 4 floor, 5 sqrt, 6 x/y2, 7 table log, 8 table sincos2pi, 9 sqrt_pn, 10 lgamma,
  * 11 log-density of the context's prior factor (int)y2[i] at x[i], src/abcdez_priors.jl:41-45). */

@@ -1019,9 +1019,33 @@ ABZ_HD double abz_tree_sum_small(const double* x, int p2) { /* p2 = power of two
  *   fixed, so any mapping of positions and columns to threads gives the same bits.
  *   The adjusted summaries are the COLUMN SUMMARIES of Y (N x d) under the same weights: no new arithmetic.
  *   What the adjustment does not do: adjusted values of a discrete parameter are no longer integers; adjusted values may leave the
- *   prior's support (the method's known caveat; transforms are the user's business); and the regression weights are Wns -- with an
+ *   prior's support (the method's known caveat, unless a TRANSFORM below bounds them); and the regression weights are Wns -- with an
  *   Epanechnikov ABC kernel those already are the kernel weights of the method, with an indicator kernel the regression is uniform
- *   over the accepted particles. */
+ *   over the accepted particles.
+ *   TRANSFORM (library version 680; `transf = "log" | "logit"` of R's abc): per parameter k one of identity, log, or logit over
+ *   (lo_k, hi_k) with lo_k < hi_k finite.  For a position that counts
+ *     u_ik = x_ik,  or  abz_log(x_ik),  or  abz_log((x_ik - lo_k) / (hi_k - x_ik))      two subtractions, one division, one log
+ *   (abz_adjust_forward).  From there on u takes the place of x in the whole adjustment: xmean (the column summaries' mean of the
+ *   dense N x d matrix U, rows that do not count +0.0 and never read), S_sx, the solve and the apply; beta, xmean and S_sx of the
+ *   result are on the transformed scale.  The adjusted value v_ik (the apply's result, or the correction's below) goes back as
+ *     y_ik = v_ik,  or  abz_exp(v_ik),  or  lo_k + (hi_k - lo_k) / (1.0 + abz_exp(-v_ik))   (abz_adjust_back)
+ *   and Y, which is what gets summarised, holds the y: log rows are >= 0, logit rows lie in the closed [lo_k, hi_k].  A counting
+ *   row outside the domain of a transform (x <= 0 for log, a zero count of a discrete parameter included; x <= lo or x >= hi for
+ *   logit) makes u -Inf, +Inf or NaN and hence xmean_k non-finite: refused before the cross pass ("adjust: transform: ... parameter
+ *   k ...").  With every transform the identity nothing changes, bit for bit.
+ *   HETEROSCEDASTIC CORRECTION (library version 680; Blum and Francois 2010, `hcorr = TRUE` of R's abc), after beta.  For a
+ *   position that counts and every k < d:
+ *     a1 = +0.0;  for j ascending: a1 = a1 + beta_jk (s_ij - smean_j);   e_ik = (u_ik - xmean_k) - a1   (abz_adjust_residual)
+ *     z_ik = abz_log(e_ik e_ik)   (abz_adjust_logres);  rows of Z that do not count are +0.0 and never read.
+ *   zmean = the column summaries' mean of Z; a non-finite zmean_k (an exactly zero or a non-finite residual) is refused by name
+ *   ("adjust: hcorr: ... parameter k ...").  S_sz[j][k] = T(abz_summary_term2(w_i, s_ij, smean_j, z_ik, zmean_k)), and
+ *     gamma = the solve above of (S_ss[cols][cols], S_sz, ridge): the same text and the same ridge as for beta.
+ *     m_k = xmean_k - acc,  acc = +0.0, for j ascending: acc = acc + beta_jk (smean_j - t_j)          (on the host, d doubles)
+ *     a2 = +0.0;  for j ascending: a2 = a2 + gamma_jk (s_ij - t_j)
+ *     v_ik = m_k + e_ik abz_exp(-0.5 a2)                                                               (abz_adjust_scaled)
+ *   i.e. the fitted value at the target plus the residual rescaled by sigma(t) / sigma(s_i); the intercept of the second regression
+ *   cancels in that ratio, which is why only gamma appears.  Without the correction v_ik is the apply's u_ik - sum_j beta_jk
+ *   (s_ij - t_j).  There is no fma anywhere outside abz_log / abz_exp. */
 ABZ_HD uint64_t abz_sample_point(uint64_t seed, uint32_t s, uint32_t draw, uint64_t q, uint64_t r) {
   const uint64_t a = (uint64_t)s * q + ((uint64_t)s < r ? (uint64_t)s : r);
   const uint64_t h = q + ((uint64_t)s < r ? 1u : 0u);
@@ -1045,6 +1069,23 @@ ABZ_HD double abz_summary_term2(double w, double xj, double mean_j, double xk, d
   return w * ((xj - mean_j) * (xk - mean_k));
 }
 ABZ_HD double abz_summary_cov_denominator(double W, double Q, int corrected) { return corrected ? W - Q / W : W; }
+/* regression adjustment, transforms and heteroscedastic correction (the text above): kind 0 identity, 1 log, 2 logit over (lo, hi) */
+#define ABZ_ADJUST_TF_NONE 0
+#define ABZ_ADJUST_TF_LOG 1
+#define ABZ_ADJUST_TF_LOGIT 2
+ABZ_HD double abz_adjust_forward(int kind, double lo, double hi, double x) {
+  if (kind == ABZ_ADJUST_TF_LOG) return abz_log(x);
+  if (kind == ABZ_ADJUST_TF_LOGIT) return abz_log((x - lo) / (hi - x));
+  return x;
+}
+ABZ_HD double abz_adjust_back(int kind, double lo, double hi, double v) {
+  if (kind == ABZ_ADJUST_TF_LOG) return abz_exp(v);
+  if (kind == ABZ_ADJUST_TF_LOGIT) return lo + (hi - lo) / (1.0 + abz_exp(-v));
+  return v;
+}
+ABZ_HD double abz_adjust_residual(double u, double umean, double a1) { return (u - umean) - a1; }
+ABZ_HD double abz_adjust_logres(double e) { return abz_log(e * e); }
+ABZ_HD double abz_adjust_scaled(double m, double e, double a2) { return m + e * abz_exp(-0.5 * a2); }
 ABZ_HD double abz_quantile_type7(double vj, double vj1, double g) { return vj + g * (vj1 - vj); }
 /* 1-based index j of the lower order statistic and the weight g of the upper one */
 ABZ_HD int64_t abz_quantile_type7_index(int64_t n, double p, double* g) {
